@@ -22,12 +22,19 @@ RCCL.
 Prints ONE JSON line on rank 0 (contract in the task statement), with
 "roofline" for the K-D-K pass kernel (kick . RZZ/RZ diagonal . kick; HIP
 events on the engine's stream over the timed region, all passes that apply
-the diagonal; every rank's rate in per_rank_GBps) and "cpu_baseline" = the
+the diagonal; every rank's rate in per_rank_GBps).  A plain run does only
+that: set up, warm up, time the steps, print the line.
+
+`--full` adds the measurements that take runs of their own, after the timed
+region (they never change the line's own numbers): "cpu_baseline" = the
 period-fused CPU restatement (oracle/dtc_oracle.c orc_autocorr_fused) on this
-host's usable cores for a bounded sample, with the CPU model.  At 8 ranks
-the line also carries "c5": the C5 configuration (one L=34 state over the 8
-GPUs) measured after the timed C2 region by a nested 8-rank job
-(run_child_ranks), or its error -- it never changes the C2 numbers.
+host's usable cores for a bounded sample, with the CPU model, and at 8 ranks
+"c5": the C5 configuration (one L=34 state over the 8 GPUs) measured by a
+nested 8-rank job (run_child_ranks), or its error.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller
+(c2/c3: fwd and echo per trajectory) as DIR/<name>.npy, float64; the inputs
+depend only on the arguments, so two builds can be compared array by array.
 """
 from __future__ import annotations
 
@@ -72,6 +79,30 @@ def periods_per_traj(T, t_offset=0):
     P = T - 1 + t_offset
     echo = sum(t + t_offset for t in range(T))
     return P + echo
+
+
+DUMP_MAX_BYTES = 60_000_000   # all files of one run together (64 MB less headers and slack)
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays the last timed step returned, as
+    <path>/<name>.npy (rank r of a multi-rank run: <name>_rank<r>.npy), float64.
+    All ranks' files together stay under DUMP_MAX_BYTES: when a rank's share
+    would not, each array is cut to a fixed, seeded sample of its flattened
+    elements (sorted indices, the same from run to run)."""
+    if not path:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_MAX_BYTES // world
+    for name, a in sorted(arrays.items()):
+        if total > budget:
+            keep = max(1, int(a.size * (budget / total)))
+            idx = np.sort(np.random.default_rng(0xD0C5).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        suffix = f"_rank{rank}" if world > 1 else ""
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
 
 
 def cpu_baseline(spec, n_traj, T_sample, threads=None, t_offset=0):
@@ -348,6 +379,13 @@ def main(argv=None):
                     help="c2/c3: trajectories per step over ALL ranks, split evenly (strong "
                          "scaling, the north_star's 1 -> 8 GPU target; default 1024); 0 = weak "
                          "scaling with --batch per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes a run of its own: the CPU "
+                         "baseline (c2, energy, ctrl; --no-cpu-baseline still drops it) and, at "
+                         "8 GPUs, the C5 sub-run attached to the c2 line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy "
+                         "(float64; ranks of a multi-GPU run add _rank<r>)")
     ap.add_argument("--spawn-selftest", action="store_true",
                     help="CPU-only check of the rank spawn path (gloo, no GPU work)")
     ap.add_argument("--selftest-nested", action="store_true",
@@ -356,11 +394,12 @@ def main(argv=None):
     ap.add_argument("--nested-timeout", type=float, default=240.0,
                     help="seconds a nested job (the C5 sub-run) may take before it is killed")
     ap.add_argument("--no-c5-subrun", action="store_true",
-                    help="c2 at 8 GPUs: skip the C5 (L=34 over 8 GPUs) sub-run that is "
-                         "attached to the line as \"c5\"")
+                    help="c2 at 8 GPUs with --full: skip the C5 (L=34 over 8 GPUs) sub-run that "
+                         "is attached to the line as \"c5\"")
     ap.add_argument("--L", type=int, default=20)
     ap.add_argument("--tf", type=int, default=30)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline (a plain run never takes it)")
     ap.add_argument("--cpu-traj", type=int, default=0,
                     help="0 = three per host thread at c2 (about 12 s on the GPU box's 16 "
                          "cores at T=30)")
@@ -440,12 +479,14 @@ def main(argv=None):
     T = args.tf
     per_traj = periods_per_traj(T)
     sums = np.zeros((2, T))
+    last = {}  # the latest step's outputs (--dump-outputs)
 
     def step(i):
         off = (rank * (args.warmup + args.steps) + i) * B
         out = eng.autocorr(spec, B, seed=0x5EED0001, traj_offset=off, batch=B)
         sums[0] += out["fwd"][0].sum(axis=0)
         sums[1] += out["echo"][0].sum(axis=0)
+        last.update(out)
 
     for i in range(args.warmup):
         step(i)
@@ -504,15 +545,18 @@ def main(argv=None):
     state_passes = sum(stats[k]["launches"] for k in (0, 1, 4)) * B
     hbm_bytes_kernels = sum(stats[k]["bytes"] for k in (0, 1, 4, 5))
 
+    dump_outputs(args.dump_outputs, last, rank, world)
+
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not c3:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not c3:
         threads = host_cpu_info()["usable_cores"]
         cpu = cpu_baseline(spec, args.cpu_traj or 3 * threads, args.cpu_tf or spec.T, threads)
 
     info = eng.device_info()
     c5 = None
     force_c5 = os.environ.get("BENCH_C5_SUBRUN") == "1"  # plumbing check on a 1-GPU box
-    if (world == 8 or force_c5) and args.config == "c2" and not args.no_c5_subrun:
+    if (args.full and (world == 8 or force_c5) and args.config == "c2"
+            and not args.no_c5_subrun):
         # SURVEY.md §8(d) C5 (one L=34 state over the 8 GPUs) as a nested 8-rank
         # job after the timed C2 region, so the node's 8-GPU run also measures
         # it; its failure or hang cannot touch the C2 line (run_child_ranks).
@@ -648,6 +692,7 @@ def main_c4(args):
     L, T, n = 28, args.tf, args.instances
     eng = pkg.DtcEngine(dev)
     sums = np.zeros((T, L))
+    last = {}  # the latest step's outputs (--dump-outputs)
 
     def step(i):
         lo = ((i * world + rank) * n) % 256
@@ -655,6 +700,7 @@ def main_c4(args):
         spec = pkg.SweepSpec(L=L, T=T, hs=hs, phis=phis, g=0.97, use_noise=0)
         out = eng.autocorr(spec, 1, want_echo=False, want_zsite=True)
         sums[:] += out["zsite"][:, 0].sum(axis=0)
+        last.update(out)
 
     for i in range(args.warmup):
         step(i)
@@ -680,6 +726,7 @@ def main_c4(args):
     if dist:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    dump_outputs(args.dump_outputs, last, rank, world)
     if rank != 0:
         if dist:
             dist.destroy_process_group()
@@ -829,6 +876,8 @@ def main_c5(args):
         dist.all_gather(ranks, mine)
     ranks = [r.cpu().numpy() for r in ranks]
     elapsed = max(float(r[4]) for r in ranks)
+    if args.steps:
+        dump_outputs(args.dump_outputs, {k: np.asarray(v) for k, v in out.items()}, rank, world)
     if rank != 0:
         if dist:
             dist.destroy_process_group()
@@ -1013,6 +1062,7 @@ def main_energy(args):
     spec = pkg.SweepSpec(L=L, T=T, hs=hs, phis=phis, g=0.97, noise_prob=0.05, use_noise=1)
     eng = pkg.DtcEngine(local_rank)
     sums = np.zeros((3, T, L))
+    last = {}  # the latest step's outputs (--dump-outputs)
 
     def step(i):
         # the estimator's trajectory sums, reduced on the device (dtc_energy_sums:
@@ -1023,8 +1073,10 @@ def main_energy(args):
         sums[0] += obs["z"][0]
         sums[1, :, :L - 1] += obs["zz"][0]
         sums[2] += obs["x"][0]
+        last.update(obs)
 
     elapsed, acc, stats = _timed(eng, dist, args.warmup, args.steps, step, sums)
+    dump_outputs(args.dump_outputs, last, rank, world)
     if rank != 0:
         if dist:
             dist.destroy_process_group()
@@ -1038,7 +1090,7 @@ def main_energy(args):
     roof["traffic"], roof["traffic_source"] = read_traffic(roof["algorithmic_bytes_per_launch"],
                                                            "_pmc_energy.json", batch=B)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_energy(spec, args.cpu_traj or 2 * _host_threads(),
                                   min(args.cpu_tf or 6, 6), _host_threads())
     res = {
@@ -1099,14 +1151,17 @@ def main_ctrl(args):
                                        prefix_cache=0 if args.no_prefix_cache else 1)
     hs, phis = load_disorder_row(L)
     res_g = np.zeros((1, T))
+    last = {}  # the latest step's outputs (--dump-outputs)
 
     def step(i):
         r = pkg.control.realtime_adaptive(L, T, hs, phis, 0.84, cfg, noise_prob=0.05,
                                           shots=shots, seed=0x5EED0001 + 7919 * (i * world + rank),
                                           engine=eng)
         res_g[0] += r.g[0]
+        last.update(forward=r.forward, echo=r.echo, g=r.g)
 
     elapsed, acc, stats = _timed(eng, dist, args.warmup, args.steps, step, res_g)
+    dump_outputs(args.dump_outputs, last, rank, world)
     if rank != 0:
         if dist:
             dist.destroy_process_group()
@@ -1119,7 +1174,7 @@ def main_ctrl(args):
                                                            "_pmc_ctrl.json", batch=shots)
     cpu = None
     # (the optimisation loop's evaluation count is data-dependent: no fixed CPU work unit)
-    if world == 1 and not args.no_cpu_baseline and not args.ctrl_opt:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.ctrl_opt:
         hs_, phis_ = load_disorder_row(L)
         s = pkg.SweepSpec(L=L, T=args.cpu_tf or 20, hs=hs_, phis=phis_, g=0.84, noise_prob=0.05,
                           use_noise=1, t_offset=1)

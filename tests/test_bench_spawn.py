@@ -91,3 +91,32 @@ def test_failed_rank_ends_the_job():
     r = _run(["--gpus", "2", "--spawn-selftest"], {"BENCH_SELFTEST_FAIL_RANK": "1"})
     assert r.returncode == 3
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 <name>.npy per array (ranks of a multi-rank
+    run add _rank<r>); past the size budget each array becomes the same seeded
+    sample of its elements on every run."""
+    import numpy as np
+
+    import bench
+
+    a = np.arange(24, dtype=np.float32).reshape(2, 3, 4)
+    b = np.linspace(0.0, 1.0, 7)
+    bench.dump_outputs(str(tmp_path / "d"), {"fwd": a, "echo": b})
+    assert sorted(os.listdir(tmp_path / "d")) == ["echo.npy", "fwd.npy"]
+    got = np.load(tmp_path / "d" / "fwd.npy")
+    assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a)
+    assert np.array_equal(np.load(tmp_path / "d" / "echo.npy"), b)
+    bench.dump_outputs(str(tmp_path / "r"), {"fwd": a}, rank=1, world=2)
+    assert os.listdir(tmp_path / "r") == ["fwd_rank1.npy"]
+    bench.dump_outputs(None, {"fwd": a})  # option not given: nothing written
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 128)   # 248 B of arrays: sampled
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), {"fwd": a, "echo": b})
+    s1 = {n: np.load(tmp_path / "s1" / n) for n in ("fwd.npy", "echo.npy")}
+    assert sum(v.nbytes for v in s1.values()) <= 128
+    assert 0 < s1["fwd.npy"].size < a.size and set(s1["fwd.npy"]) <= set(a.ravel().tolist())
+    for n, v in s1.items():
+        assert np.array_equal(v, np.load(tmp_path / "s2" / n))

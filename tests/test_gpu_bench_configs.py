@@ -57,12 +57,35 @@ def test_ctrl_line():
 
 
 def test_c5_subrun_forced():
-    """The nested C5 job of the 8-GPU line (BENCH_C5_SUBRUN=1 forces it at one
-    rank: 8 virtual shards of L=31)."""
-    d = _run(["--steps", "1", "--warmup", "0", "--strong-total", "32", "--tf", "4",
+    """The nested C5 job of the 8-GPU --full line (BENCH_C5_SUBRUN=1 forces it
+    at one rank: 8 virtual shards of L=31)."""
+    d = _run(["--full", "--steps", "1", "--warmup", "0", "--strong-total", "32", "--tf", "4",
               "--no-cpu-baseline"], {"BENCH_C5_SUBRUN": "1"})
     assert "error" not in d["c5"], d["c5"]
     assert d["c5"]["config"]["shards"] == 8
     assert abs(d["c5"]["z_t1_mean"] - COS) < 1e-12
     # (in place on one GPU the exchange is fused into the slice kicks: no window)
     assert d["c5"]["exchange"]["per_period_ms"] > 0 or d["c5"]["exchange"]["fused_into_kick_pass"]
+
+
+def test_plain_line_is_lean_and_dumps_last_step(tmp_path):
+    """A plain run stops after its timed steps (no CPU baseline, no sub-run) and
+    --dump-outputs writes what its last step returned: with one timed step the
+    line's trajectory means are the means of the dumped rows."""
+    import numpy as np
+
+    d = _run(["--gpus", "1", "--steps", "1", "--warmup", "1", "--strong-total", "32", "--tf", "4",
+              "--dump-outputs", str(tmp_path / "out")])
+    assert "cpu_baseline" not in d and "c5" not in d
+    assert d["steps"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["echo.npy", "fwd.npy"]
+    for k in ("fwd", "echo"):
+        a = np.load(tmp_path / "out" / (k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (1, 32, 4)
+        assert np.abs(a[0].mean(axis=0) - np.array(d["autocorr_t0_3"][k])).max() < 1e-12
+
+
+def test_full_line_carries_cpu_baseline():
+    d = _run(["--full", "--steps", "1", "--warmup", "0", "--strong-total", "32", "--tf", "4",
+              "--cpu-traj", "2"])
+    assert d["cpu_baseline"]["value"] > 0 and d["value"] > 0

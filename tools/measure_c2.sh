@@ -8,7 +8,7 @@ set -o pipefail
 TAG=$1; shift
 R=$(pwd); O=$R/gpurun_out
 mkdir -p $O
-timeout -k 10 300 python -u bench.py "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { echo "bench failed"; tail -5 $O/${TAG}_bench.err; exit 1; }
 cat $O/${TAG}_bench.json
 export TMPDIR=/tmp
 cd /tmp

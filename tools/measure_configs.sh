@@ -7,7 +7,7 @@ TAG=$1; shift
 CONFIGS=${@:-c3 c4 energy ctrl c5}
 R=$(pwd); O=$R/gpurun_out; mkdir -p $O
 for c in $CONFIGS; do
-  timeout -k 10 300 python -u bench.py --config $c > $O/${TAG}_${c}_bench.json 2> $O/${TAG}_${c}_bench.err || { echo "$c failed"; tail -5 $O/${TAG}_${c}_bench.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --config $c > $O/${TAG}_${c}_bench.json 2> $O/${TAG}_${c}_bench.err || { echo "$c failed"; tail -5 $O/${TAG}_${c}_bench.err; exit 1; }
   python -c "import json,sys; d=json.load(open('$O/${TAG}_${c}_bench.json')); r=d.get('roofline',{}); print('$c', round(d['value'],2), d['unit'], round(r.get('achieved',0)), r.get('avg_launch_ms'))"
 done
 export TMPDIR=/tmp
