@@ -145,6 +145,42 @@ int dtc_autocorr_device(dtc_ctx* ctx, const dtc_problem* prob, const dtc_device_
                         uint64_t seed, int64_t traj_offset, int32_t n_traj, double* fwd,
                         double* echo, double* zsite);
 
+/* Two-qubit depolarizing noise on the chain's bonds: Aer's
+ * depolarizing_error(p, 2), E(rho) = (1-p) rho + p I/4, after every RZZ of a
+ * forward period and every RZZ^+ of an inverse period -- what a user writes as
+ * noise_model.add_all_qubit_quantum_error(depolarizing_error(p2, 2), ["rzz"])
+ * next to fast.py:84-86.  As a Pauli mixture: II with weight 1 - 15p/16, each
+ * of the 15 other pairs p/16; p in [0, 16/15].  The ancilla is untouched (the
+ * fold of SURVEY.md section 0.6 stays exact for a channel on the chain only).
+ * Gate order as in the reference: forward period (fast.py:111-121) kicks, RZZ
+ * on even bonds, RZZ on odd bonds, RZ; inverse period (fast.py:140-143) RZ^+,
+ * RZZ^+ on odd bonds, RZZ^+ on even bonds, kick^+.
+ * One Philox draw per (seed, trajectory, stream, counter, bond), (stream,
+ * counter) those of the adjacent kick layer: forward period p (0, p), step k
+ * of the echo at t (1 + t, k); disjoint from the kick draws, which stay
+ * exactly as they are.  Rows do not depend on batching or sharding. */
+typedef struct dtc_bond_noise {
+  const double* p_bond;   /* [L-1], depolarizing_error(p, 2) parameter after the RZZ of bond b */
+  int32_t reserved[2];
+} dtc_bond_noise;
+
+/* dtc_autocorr with the channel above after every RZZ / RZZ^+.  dv must be NULL in this
+ * version (DTC_EINVAL otherwise).  bond == NULL or every p_bond == 0: exactly dtc_autocorr.
+ * DTC_EINVAL also for p_bond outside [0, 16/15], prob->t_offset != 0, and a forward
+ * prefix in place on the ctx (dtc_prefix_build; release it first).  Bond runs use the
+ * plain chains (no light-cone end, no dual pass, DTC_SPLIT13 ignored); each diagonal
+ * pass is preceded by one launch that builds its per-state factor tables (counted
+ * under DTC_KERNEL_INIT when profiling). */
+int dtc_autocorr_bond(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                      const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                      int64_t traj_offset, int32_t n_traj, double* fwd, double* echo,
+                      double* zsite);
+
+/* Host only, no device: the Pauli pairs drawn for one diagonal layer of one trajectory,
+ * codes[b] = P_site_b + 4 * P_site_b+1 with 0 = I, 1 = X, 2 = Y, 3 = Z  (codes: [L-1]). */
+int dtc_bond_draws(const dtc_bond_noise* bond, int32_t L, uint64_t seed, int64_t traj,
+                   uint32_t stream, uint32_t counter, int32_t* codes);
+
 /* Unit-test hook: apply n_periods Floquet periods to one host state vector
  * of 2^L complex128 amplitudes (in/out).  Forward: periods first_period,
  * first_period+1, ... (1-based rows of prob->kick), RNG stream `stream`,
@@ -321,7 +357,7 @@ int dtc_energy_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* nois
 #define DTC_KERNEL_LO_PASS 0   /* fused RZZ+RZ diagonal + low-site kick pass */
 #define DTC_KERNEL_HI_PASS 1   /* high-site kick pass                        */
 #define DTC_KERNEL_REDUCE 2    /* per-state observable reduction             */
-#define DTC_KERNEL_INIT 3      /* basis-state preparation                    */
+#define DTC_KERNEL_INIT 3      /* preparation: bond-noise diagonal table builder */
 #define DTC_KERNEL_FINAL_PASS 4 /* last pass of an echo chain: measure, no store */
 #define DTC_KERNEL_EXCHANGE 5  /* virtual ranks' in-place slice exchange        */
 #define DTC_KERNEL_KINDS 6

@@ -14,7 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libdtc_hip.so")
-KERNEL_KINDS = 6  # DTC_KERNEL_KINDS: lo pass, hi pass, reduce, init, final (measure-only) pass,
+KERNEL_KINDS = 6  # DTC_KERNEL_KINDS: lo pass, hi pass, reduce, bond tables, final (measure-only) pass,
                   # virtual-rank exchange
 ABI_VERSION = 12  # DTC_ABI_VERSION of include/dtc.h this binding matches
 
@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = (
     "dtc_shard_kick_exchange_slice",
     "dtc_get_stream",
     "dtc_synchronize",
+    "dtc_autocorr_bond",
+    "dtc_bond_draws",
 )
 
 KERNEL_LO_PASS = 0
@@ -61,7 +63,7 @@ KERNEL_NAMES = {
     KERNEL_LO_PASS: "pass_kernel<diag>  (fused RZZ+RZ diagonal + sites 0..11 kick)",
     KERNEL_HI_PASS: "pass_kernel<none>  (kick on sites >= 12)",
     KERNEL_REDUCE: "reduce_kernel",
-    KERNEL_INIT: "set_basis_kernel",
+    KERNEL_INIT: "bond_diag_kernel (bond-noise diagonal tables per state, dtc_autocorr_bond)",
     KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split (measure only, no store)",
     KERNEL_EXCHANGE: "exchange_swap_kernel (virtual ranks' in-place slice exchange)",
 }
@@ -111,6 +113,15 @@ class DtcDeviceNoise(ctypes.Structure):
         ("anc_factor", ctypes.c_double),
         ("readout_p01", ctypes.c_double),
         ("readout_p10", ctypes.c_double),
+    ]
+
+
+class DtcBondNoise(ctypes.Structure):
+    """Mirror of ``dtc_bond_noise`` (include/dtc.h)."""
+
+    _fields_ = [
+        ("p_bond", _dp),
+        ("reserved", ctypes.c_int32 * 2),
     ]
 
 
@@ -244,6 +255,14 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
             ctypes.c_int64, ctypes.c_int32, _dp, _dp,
         ]
         lib.dtc_prefix_release.argtypes = [ctypes.c_void_p]
+        lib.dtc_autocorr_bond.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), P(DtcDeviceNoise), P(DtcBondNoise),
+            ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, _dp, _dp, _dp,
+        ]
+        lib.dtc_bond_draws.argtypes = [
+            P(DtcBondNoise), ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32,
+            ctypes.c_uint32, P(ctypes.c_int32),
+        ]
         lib.dtc_plan_groups.argtypes = [ctypes.c_int32, P(ctypes.c_uint64), ctypes.c_int32]
         for name in EXPORTED_SYMBOLS:
             if name not in ("dtc_last_error", "dtc_abi_version"):

@@ -42,11 +42,13 @@ class QuantumError:
 
 
 def depolarizing_error(param: float, num_qubits: int) -> QuantumError:
-    """qiskit_aer.noise.depolarizing_error: rho -> (1-p) rho + p I/2^n."""
-    if num_qubits != 1:
-        raise NotImplementedError("only single-qubit depolarizing errors occur on this path")
-    if not 0.0 <= param <= 4.0 / 3.0:
-        raise ValueError("depolarizing parameter must be in [0, 4/3]")
+    """qiskit_aer.noise.depolarizing_error: rho -> (1-p) rho + p I/2^n.  The
+    two-qubit error is the bond noise of the engine (on ``["rzz"]`` only)."""
+    if num_qubits not in (1, 2):
+        raise NotImplementedError("only one- and two-qubit depolarizing errors occur on this path")
+    hi = 4.0 / 3.0 if num_qubits == 1 else 16.0 / 15.0
+    if not 0.0 <= param <= hi:
+        raise ValueError(f"depolarizing parameter must be in [0, {'4/3' if num_qubits == 1 else '16/15'}]")
     return QuantumError("depolarizing", param, num_qubits)
 
 
@@ -60,6 +62,13 @@ class NoiseModel:
     def add_all_qubit_quantum_error(self, error: QuantumError, instructions, warnings=True):
         if isinstance(instructions, str):
             instructions = [instructions]
+        if error.num_qubits == 2:
+            # the engine's bond noise: after every RZZ / RZZ^+ of the chain
+            if list(instructions) != ["rzz"]:
+                raise NotImplementedError(
+                    "a two-qubit error is supported on [\"rzz\"] only (the chain's bonds)")
+            self.bond_error = error
+            return
         for g in instructions:
             self._errors[g] = error
 
@@ -78,17 +87,19 @@ class NoiseModel:
         return nm
 
     device_calibration = None
+    bond_error = None  # depolarizing_error(p, 2) on ["rzz"]
 
     @property
     def noise_instructions(self):
-        return sorted(self._errors)
+        return sorted(list(self._errors) + (["rzz"] if self.bond_error is not None else []))
 
     def error_for(self, gate: str):
         carrier = _NOISE_CARRIER.get(gate)
         return self._errors.get(carrier) if carrier else None
 
     def is_ideal(self):
-        return not self._errors and self.device_calibration is None
+        return (not self._errors and self.device_calibration is None
+                and self.bond_error is None)
 
 
 class FakeDevice:
@@ -118,6 +129,7 @@ class FoldedCircuit:
     kick_noisy: bool
     n_anc_noisy: int
     prep_noisy: bool
+    bond_p: float = 0.0     # depolarizing_error(p, 2) after every RZZ / RZZ^+ (0: none)
 
 
 def _site_of(q: int, anc: int) -> int:
@@ -278,11 +290,12 @@ def fold_circuit(circ: QuantumCircuit, noise: NoiseModel | None) -> FoldedCircui
     n_anc = 6 if noise.error_for("h") is not None else 0
     return FoldedCircuit(L=L, n_fwd=nf, echo=ni > 0, probe=probe, init_mask=init,
                          hs=hs[None, :], phis=ph[None, : max(L - 1, 1)], kick=kick,
-                         kick_noisy=kick_noisy, n_anc_noisy=n_anc, prep_noisy=prep_noisy)
+                         kick_noisy=kick_noisy, n_anc_noisy=n_anc, prep_noisy=prep_noisy,
+                         bond_p=noise.bond_error.p if noise.bond_error is not None else 0.0)
 
 
 def _noise_p(noise: NoiseModel | None) -> float:
-    if noise is None or noise.is_ideal():
+    if noise is None or not noise._errors:
         return 0.0
     ps = {e.p for e in noise._errors.values()}
     kinds = {e.kind for e in noise._errors.values()}
@@ -351,6 +364,8 @@ class DtcSimulator:
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
         cal = getattr(self.noise_model, "device_calibration", None)
+        if cal is not None and getattr(self.noise_model, "bond_error", None) is not None:
+            raise NotImplementedError("bond noise together with device-like noise")
         p = 0.0 if cal is not None else _noise_p(self.noise_model)
         eng = get_engine(self.device_index)
         counts, expv = [], []
@@ -373,8 +388,9 @@ class DtcSimulator:
             T = f.n_fwd + 1
             spec = SweepSpec(L=f.L, T=T, hs=f.hs, phis=f.phis, kick=f.kick,
                              noise_prob=pk, use_noise=1, probe_site=f.probe,
-                             init_mask_value=f.init_mask)
-            n_traj = shots if pk > 0 else 1
+                             init_mask_value=f.init_mask,
+                             bond_noise=f.bond_p if (f.bond_p > 0 and f.L > 1) else None)
+            n_traj = shots if (pk > 0 or spec.has_bond_noise) else 1
             out = _run_single(eng, spec, f, n_traj, seed + 7919 * (self._calls + ci), p)
             a = out  # per-trajectory ancilla expectations at t = n_fwd
             rng = np.random.default_rng([seed, self._calls, ci])
@@ -406,10 +422,20 @@ def _run_single(eng: DtcEngine, spec: SweepSpec, f: FoldedCircuit, n_traj: int, 
     nz.n_anc = 0
     fwd = np.zeros((1, n_traj, T))
     echo = np.zeros((1, n_traj, T))
-    _capi.check(eng._lib.dtc_autocorr(
-        eng._ctx, ctypes.byref(pr), ctypes.byref(nz), ctypes.c_uint64(seed & (2**64 - 1)),
-        ctypes.c_int64(0), ctypes.c_int32(n_traj), _capi.as_dptr(fwd if not f.echo else None),
-        _capi.as_dptr(echo if f.echo else None), None))
+    outs = (_capi.as_dptr(fwd if not f.echo else None), _capi.as_dptr(echo if f.echo else None),
+            None)
+    if spec.has_bond_noise:
+        from .engine import bond_struct
+
+        bd = bond_struct(spec.bond_noise)
+        _capi.check(eng._lib.dtc_autocorr_bond(
+            eng._ctx, ctypes.byref(pr), ctypes.byref(nz), None, ctypes.byref(bd),
+            ctypes.c_uint64(seed & (2**64 - 1)), ctypes.c_int64(0), ctypes.c_int32(n_traj),
+            *outs))
+    else:
+        _capi.check(eng._lib.dtc_autocorr(
+            eng._ctx, ctypes.byref(pr), ctypes.byref(nz), ctypes.c_uint64(seed & (2**64 - 1)),
+            ctypes.c_int64(0), ctypes.c_int32(n_traj), *outs))
     a = (echo if f.echo else fwd)[0, :, T - 1]
     return a * (1.0 - p_anc) ** f.n_anc_noisy
 

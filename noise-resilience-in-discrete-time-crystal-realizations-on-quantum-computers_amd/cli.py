@@ -44,6 +44,9 @@ def build_parser():
     p.add_argument("--g", type=float, default=0.97, help="kick strength g (RX(pi g))")
     p.add_argument("--noise_prob", type=float, default=0.05, help="depolarizing probability")
     p.add_argument("--use_noise", type=int, default=1, help="0=no noise, 1=apply noise")
+    p.add_argument("--bond_noise_prob", type=float, default=0.0,
+                   help="depolarizing_error(p, 2) after every RZZ / RZZ^+ of the chain (0 = none; "
+                        "above 0 the file name gains _bond{p})")
     p.add_argument("--initial_state", type=str, default="vacuum", choices=["vacuum", "neel"])
     p.add_argument("--use_fakebackend", type=int, default=0,
                    help="1 = device-like noise (thermal relaxation + depolarizing + read-out) "
@@ -86,13 +89,16 @@ def main(argv=None):
     spec = SweepSpec(L=L, T=T, hs=hs, phis=phis, g=args.g, polarization=args.polarization,
                      circular_frequency=args.circular_frequency,
                      initial_state=args.initial_state, noise_prob=args.noise_prob,
-                     use_noise=args.use_noise, t_offset=args.t_offset, device=device)
+                     use_noise=args.use_noise, t_offset=args.t_offset, device=device,
+                     bond_noise=args.bond_noise_prob if args.bond_noise_prob > 0 else None)
+    if spec.has_bond_noise and device is not None:
+        raise SystemExit("--bond_noise_prob does not combine with --use_fakebackend 1")
     shots = args.shots or None
-    if spec.p == 0 and device is None:
+    if spec.p == 0 and device is None and not spec.has_bond_noise:
         n_traj = 1
     else:
         n_traj = args.trajectories or (shots or 1024)
-    if shots and spec.p > 0 and device is None and n_traj != shots:
+    if shots and (spec.p > 0 or spec.has_bond_noise) and device is None and n_traj != shots:
         raise SystemExit("--trajectories must equal --shots when emulating shots (use --shots 0 "
                          "for trajectory means)")
 
@@ -116,7 +122,7 @@ def main(argv=None):
     folder = os.path.join(args.out_dir, sw.folder_name(L, args.noise_prob, args.use_fakebackend))
     name = sw.autocorr_csv_name(args.initial_state, args.g, L, args.inst, args.tf, args.randomphi,
                                 args.phi_delta, args.phi_amplitude, args.noise_prob,
-                                args.use_noise)
+                                args.use_noise, bond_noise_prob=args.bond_noise_prob)
     path = sw.write_autocorr_csv(os.path.join(folder, name), np.arange(0, T),
                                  res.av_autocorr, res.av_autocorr_echo)
     print(f"Autocorrelation data saved to {path}")

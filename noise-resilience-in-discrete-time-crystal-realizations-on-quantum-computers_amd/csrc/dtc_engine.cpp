@@ -89,6 +89,9 @@ struct dtc_ctx {
   DevBuf red_scratch;  // split sums of the two-stage tile reduction (large states)
   DevBuf recs, recs1, pk;               // kick records (batch schedule / single pass), pass list
   DevBuf dev_thr, dev_jump, dev_kraus;  // device-like noise tables (dtc_autocorr_device)
+  // bond noise (dtc_autocorr_bond): draw thresholds [L-1], the angles h | phi of
+  // every instance, and the current diagonal layer's per-state factor tables
+  DevBuf bond_thr, bond_ang, bond_diag;
   std::vector<dtc::PassKick> pk_host;   // staged pass list (alive until the stream syncs)
   // forward prefix (dtc_prefix_build): every trajectory's state after
   // prefix_periods periods, and what it was built from
@@ -351,6 +354,13 @@ struct RunCfg {
   const uint32_t* dev_thr = nullptr;   // device copies
   const uint32_t* dev_jump = nullptr;
   const double* dev_kraus = nullptr;
+  // two-qubit depolarizing noise on the bonds (dtc_autocorr_bond): thresholds of
+  // sample_bond per bond (host and device), the instances' angles on the device
+  bool bond = false;
+  std::vector<uint32_t> bond_thr_host;
+  const uint32_t* bond_thr = nullptr;
+  const double* bond_h = nullptr;
+  const double* bond_phi = nullptr;
 };
 
 // ---- layer chains ---------------------------------------------------------
@@ -480,6 +490,7 @@ dtc::PrepArgs prep_args(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int
   P.dev_thr = rc.dev_thr;
   P.dev_thr_jump = rc.dev_jump;
   P.dev_kraus = rc.dev_kraus;
+  P.bond_thr = rc.bond_thr;
   return P;
 }
 
@@ -577,7 +588,8 @@ int launch_pass_spec(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int ba
                      int meas_at_end, int n_obs, double* meas_out, int64_t meas_stride,
                      const dtc::KickRec* recs = nullptr, int meas_parts = 0,
                      int no_store = 0, const int64_t* basis = nullptr, int swap_k = 0,
-                     const dtc::KickRec* recs2 = nullptr, double2* dst2 = nullptr) {
+                     const dtc::KickRec* recs2 = nullptr, double2* dst2 = nullptr,
+                     const double2* state_diag = nullptr) {
   const int shape = pass_shape(ps);
   if (shape < 0) return fail(DTC_EINVAL, "internal: empty pass");
   const int kind = pass_kind(rc, ps, shape);
@@ -592,6 +604,13 @@ int launch_pass_spec(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int ba
     recs = P.out;
   }
   dtc::PassArgs A = base_args(ctx, rc, batch_start);
+  if (state_diag) {
+    // bond noise: one table per state of the batch (launch_bond_diag), which
+    // the kernels' instance lookup (batch_start + b) / n_traj finds at b
+    A.diag = state_diag;
+    A.batch_start = 0;
+    A.n_traj = 1;
+  }
   const Group g = pass_group(rc.pl, ps);
 #ifdef DTC_PHASE_TIMING
   if (const char* e = std::getenv("DTC_DBG_GROUP"))
@@ -722,7 +741,51 @@ struct Launch {
   // tile after the pre-kick, kicked by ps2's post, goes to dst2
   double2* dst2 = nullptr;
   PassSpec ps2{};
+  // bond noise: the pass's diagonal is the noisy layer drawn at (bond_stream,
+  // bond_counter), of a forward (0) or an inverse (1) period
+  int bond_diag = 0;
+  uint32_t bond_stream = 0, bond_counter = 0;
+  int bond_inv = 0;
 };
+
+// The per-state diagonal tables of launch l's noisy layer, into ctx->bond_diag
+// (one buffer: the stream orders the builder after the pass that read the
+// previous layer's tables).
+int launch_bond_tables(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
+                       const Launch& l) {
+  dtc::BondDiagArgs B{};
+  B.out = (double2*)ctx->bond_diag.p;
+  B.h = rc.bond_h;
+  B.phi = rc.bond_phi;
+  B.thr = rc.bond_thr;
+  B.L = rc.pl.L;
+  B.L_eff = rc.pl.L_eff;
+  B.n_chunks = rc.pl.n_chunks;
+  B.diag_stride = rc.pl.diag_stride;
+  B.batch = batch;
+  B.batch_start = batch_start;
+  B.n_traj = rc.n_traj;
+  B.traj_offset = rc.traj_offset;
+  B.seed = rc.seed;
+  B.stream = l.bond_stream;
+  B.counter = l.bond_counter;
+  B.inverse = l.bond_inv;
+  if (ctx->bond_diag.n < (size_t)batch * B.diag_stride * sizeof(double2))
+    return fail(DTC_EINVAL, "internal: bond table buffer too small");
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->prof) {
+    e0 = get_event(ctx);
+    e1 = get_event(ctx);
+    DTC_HIP(hipEventRecord(e0, ctx->stream));
+  }
+  DTC_HIP(dtc::launch_bond_diag(B, ctx->stream));
+  if (ctx->prof) {
+    DTC_HIP(hipEventRecord(e1, ctx->stream));
+    ctx->pending.push_back(Pending{DTC_KERNEL_INIT, e0, e1,
+                                   (double)batch * B.diag_stride * sizeof(double2)});
+  }
+  return DTC_OK;
+}
 
 int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
                  const std::vector<Launch>& L) {
@@ -768,10 +831,12 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
     for (size_t i = i0; i < i1; ++i) {
       const Launch& l = L[i];
       const dtc::KickRec* rec = P.out + (row0[i] - row0[i0]) * batch * dtc::kRecPerState;
+      if (l.bond_diag) DTC_TRY(launch_bond_tables(ctx, rc, batch_start, batch, l));
       DTC_TRY(launch_pass_spec(ctx, rc, batch_start, batch, l.ps, l.src, l.dst, l.meas_mode,
                                l.meas_at_end, l.n_obs, l.meas_out, l.meas_stride, rec, 0,
                                l.no_store, l.basis, 0,
-                               l.dst2 ? rec + batch * dtc::kRecPerState : nullptr, l.dst2));
+                               l.dst2 ? rec + batch * dtc::kRecPerState : nullptr, l.dst2,
+                               l.bond_diag ? (const double2*)ctx->bond_diag.p : nullptr));
     }
     i0 = i1;
   }
@@ -1379,9 +1444,12 @@ int dtc_close(dtc_ctx* ctx) {
   release(ctx->recs);
   release(ctx->recs1);
   release(ctx->pk);
+  release(ctx->bond_diag);
   release(ctx->dev_thr);
   release(ctx->dev_jump);
   release(ctx->dev_kraus);
+  release(ctx->bond_thr);
+  release(ctx->bond_ang);
   for (auto& e : ctx->shard_cache) release(e.diag);
   for (auto& e : ctx->shard_maps) release(e.diag);
   release(ctx->shard_kick);
@@ -1402,6 +1470,7 @@ int dtc_release_buffers(dtc_ctx* ctx) {
   release(ctx->recs);
   release(ctx->recs1);
   release(ctx->pk);
+  release(ctx->bond_diag);
   return DTC_OK;
 }
 
@@ -1522,6 +1591,58 @@ int setup_device_noise(dtc_ctx* ctx, const dtc_problem* pr, const dtc_device_noi
   return DTC_OK;
 }
 
+// Thresholds of sample_bond (dtc_rng.h) for p_bond[0 .. L-2]: an error happens
+// with probability 15 p / 16.
+int bond_thresholds(const dtc_bond_noise* bond, int L, std::vector<uint32_t>& thr) {
+  thr.assign(L > 1 ? L - 1 : 0, 0u);
+  if (!bond) return DTC_OK;
+  if (L > 1 && !bond->p_bond) return fail(DTC_EINVAL, "null p_bond");
+  for (int b = 0; b + 1 < L; ++b) {
+    const double p = bond->p_bond[b];
+    if (!(p >= 0.0 && p <= 16.0 / 15.0)) return fail(DTC_EINVAL, "p_bond must be in [0, 16/15]");
+    double v = std::floor(15.0 * p / 16.0 * 4294967296.0 + 0.5);
+    if (v >= 4294967295.0) v = 4294967295.0;
+    thr[b] = (uint32_t)v;
+  }
+  return DTC_OK;
+}
+
+// Device tables of dtc_bond_noise: the thresholds and the instances' angles
+// (the table builder signs them per state, dtc_bond.hip).
+int setup_bond_noise(dtc_ctx* ctx, const dtc_problem* pr, const dtc_bond_noise* bond, RunCfg& rc) {
+  const int L = pr->L;
+  DTC_TRY(bond_thresholds(bond, L, rc.bond_thr_host));
+  const size_t nh = (size_t)pr->n_inst * L, np = (size_t)pr->n_inst * (L - 1);
+  DTC_TRY(ensure(ctx->bond_thr, rc.bond_thr_host.size() * sizeof(uint32_t)));
+  DTC_TRY(ensure(ctx->bond_ang, (nh + np) * sizeof(double)));
+  DTC_HIP(hipMemcpyAsync(ctx->bond_thr.p, rc.bond_thr_host.data(),
+                         rc.bond_thr_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                         ctx->stream));
+  DTC_HIP(hipMemcpyAsync(ctx->bond_ang.p, pr->h, nh * sizeof(double), hipMemcpyHostToDevice,
+                         ctx->stream));
+  DTC_HIP(hipMemcpyAsync((double*)ctx->bond_ang.p + nh, pr->phi, np * sizeof(double),
+                         hipMemcpyHostToDevice, ctx->stream));
+  DTC_HIP(hipStreamSynchronize(ctx->stream));
+  rc.bond = true;
+  rc.bond_thr = (const uint32_t*)ctx->bond_thr.p;
+  rc.bond_h = (const double*)ctx->bond_ang.p;
+  rc.bond_phi = (const double*)ctx->bond_ang.p + nh;
+  return DTC_OK;
+}
+
+// X content per site of the outgoing Pauli of one noisy diagonal layer: site i
+// carries (right part of bond i-1's error) (left part of bond i's error).
+uint64_t bond_out_x(const RunCfg& rc, uint64_t traj, uint32_t stream, uint32_t counter) {
+  uint64_t m = 0;
+  for (int b = 0; b + 1 < rc.pl.L; ++b) {
+    const int code = dtc::sample_bond(rc.seed, traj, stream, counter, (uint32_t)b,
+                                      rc.bond_thr_host[b]);
+    if (dtc::pauli_has_x(code & 3)) m ^= 1ull << b;
+    if (dtc::pauli_has_x(code >> 2)) m ^= 1ull << (b + 1);
+  }
+  return m;
+}
+
 // What a prefix must match: the instances' angles and the kick rows of its
 // periods (FNV-1a over the bytes), so a continuation inverts the same periods.
 uint64_t prefix_hash(const dtc_problem* pr, int n_periods) {
@@ -1542,7 +1663,8 @@ uint64_t prefix_hash(const dtc_problem* pr, int n_periods) {
 
 int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                   const dtc_device_noise* dv, uint64_t seed, int64_t traj_offset, int32_t n_traj,
-                  double* fwd, double* echo, double* zsite, bool use_prefix = false) {
+                  double* fwd, double* echo, double* zsite, bool use_prefix = false,
+                  const dtc_bond_noise* bond = nullptr) {
   if (!ctx) return fail(DTC_EINVAL, "null ctx");
   DTC_TRY(check_problem(pr, nz));
   if (n_traj < 1) return fail(DTC_EINVAL, "n_traj must be >= 1");
@@ -1561,12 +1683,13 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   {
     // the 13 / 7 split where its kernels cover every pass: L = 20, unitary
     // factored kicks (RX / RY rows), the probe measurement only, no prefix
-    bool s13 = ctx->split13 && pr->L == 20 && !dv && !zsite && !use_prefix;
+    bool s13 = ctx->split13 && pr->L == 20 && !dv && !zsite && !use_prefix && !bond;
     for (int k : rc.row_kind) s13 = s13 && (k == dtc::kKindRX || k == dtc::kKindRY);
     rc.pl = make_plan(pr->L, false, s13);
   }
   thresholds(nz->p, &rc.thr1, &rc.thr2, &rc.thr3);
   if (dv) DTC_TRY(setup_device_noise(ctx, pr, dv, rc));
+  if (bond) DTC_TRY(setup_bond_noise(ctx, pr, bond, rc));
   const Plan& pl = rc.pl;
   const int T = pr->T, L = pr->L;
   const int P = T - 1 + pr->t_offset;
@@ -1639,6 +1762,7 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   DTC_TRY(ensure(ctx->vals_f, (size_t)B * T * n_obs_f * sizeof(double)));
   if (want_e) DTC_TRY(ensure(ctx->vals_e, (size_t)B * T * 2 * sizeof(double)));
   DTC_TRY(ensure(ctx->basis, (size_t)B * sizeof(int64_t)));
+  if (rc.bond) DTC_TRY(ensure(ctx->bond_diag, (size_t)B * pl.diag_stride * sizeof(double2)));
 
   DTC_TRY(ensure_host(ctx->host_f, (size_t)B * T * n_obs_f));
   if (want_e) DTC_TRY(ensure_host(ctx->host_e, (size_t)B * T * 2));
@@ -1674,7 +1798,11 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                              ctx->stream));
 
     // DTC_NO_LIGHTCONE=1: keep the chains' last two passes (development A/B)
-    const bool lc_enabled = ctx->lightcone;
+    // Bond noise runs the plain chains: the cone tables are per instance, and
+    // the dual fold would conjugate the forward layer's table, where the
+    // chain's first D^* is a noisy layer of its own
+    const bool lc_enabled = ctx->lightcone && !rc.bond;
+    const bool dual_enabled = ctx->dual && !rc.bond;
     // Forward chain K_1 D K_2 D ... K_P D; after each D_p: measure t = p - t_offset
     // and branch the echo at t off F.  The whole batch schedule is built first.
     // Device-like noise (r5): the forward runs one kick layer ahead, one pass
@@ -1692,6 +1820,13 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     if (P > n_pre) {
       Chain fw = forward_chain(pl, n_pre + 1, P - n_pre, dtc::kStreamForward);
       fw.post_after_d = !dev_kd;
+      // bond noise: period q's kicks take the outgoing Pauli of layer q - 1
+      if (rc.bond)
+        for (size_t k = 1; k < fw.X.size(); ++k) {
+          fw.X[k].bond_on = 1u;
+          fw.X[k].bond_stream = dtc::kStreamForward;
+          fw.X[k].bond_counter = (uint32_t)(n_pre + k);
+        }
       // start on a group without the probe site: every echo chain then ends
       // with its kick-only pass on such a group, which the probe does not need
       // (two groups: the closing groups alternate with p, see below)
@@ -1709,10 +1844,35 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                                n_obs_f,
                                meas ? (double*)ctx->vals_f.p + (size_t)t * n_obs_f : nullptr,
                                (int64_t)T * n_obs_f});
+        if (rc.bond && closes) {
+          sched.back().bond_diag = 1;
+          sched.back().bond_stream = dtc::kStreamForward;
+          sched.back().bond_counter = (uint32_t)p;
+        }
         if (!closes || !want_e || t < 0 || t < pr->t_first) continue;
         std::vector<int> ahead(pl.groups.size());
         for (size_t g = 0; g < pl.groups.size(); ++g) ahead[g] = fw.kc[g] > ps.d_index;
         Chain ec = echo_chain(pl, p, (uint32_t)(1 + t), ahead);
+        if (rc.bond) {
+          // The echo starts from P_t D'_t ...: on a group that ran ahead, F
+          // holds K_{p+1} P_t and X_0's undo (without the Pauli) leaves P_t; on
+          // the others X_0 is P_t alone (patched below).  Step k's kicks take
+          // the outgoing Pauli of the chain's k-th noisy D^*.
+          std::fill(ec.kc.begin(), ec.kc.end(), 0);
+          if (pl.groups.size() == 2) {
+            // the chain's p + 2 passes alternate between the two groups from its
+            // kick-only first pass: start so that the trailing kick-only pass lands
+            // on the group without the probe, where it is dropped (below)
+            const int gp = ((group_bits(pl.groups[0]) >> pr->probe_site) & 1ull) ? 0 : 1;
+            ec.prio.assign(2, 1);
+            ec.prio[(p % 2) ? 1 - gp : gp] = 0;
+          }
+          for (size_t k = 1; k < ec.X.size(); ++k) {
+            ec.X[k].bond_on = 1u;
+            ec.X[k].bond_stream = (uint32_t)(1 + t);
+            ec.X[k].bond_counter = (uint32_t)k;
+          }
+        }
         // run ahead under device-like noise, a chain whose first pass undoes
         // the forward's run-ahead layer must fold (the undo of a Kraus kick
         // cannot run); the sweep's last chain, after a K-D, has none
@@ -1729,7 +1889,20 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
         const size_t chain0 = sched.size();
         while (!ec.done()) {
           PassSpec es = next_pass(ec);
+          if (rc.bond && es.pre.enabled && es.pre.mode == dtc::kKickUndo && !ahead[es.group]) {
+            es.pre.mode = dtc::kKickBondPauli;
+            es.pre.row = p - 1;
+            es.pre.bond_on = 1u;
+            es.pre.bond_stream = dtc::kStreamForward;
+            es.pre.bond_counter = (uint32_t)p;
+          }
           sched.push_back(Launch{es, src, E, dtc::kMeasNone, 1, 2, nullptr, (int64_t)T * 2});
+          if (rc.bond && es.diag != dtc::kDiagNone) {
+            sched.back().bond_diag = 1;
+            sched.back().bond_stream = (uint32_t)(1 + t);
+            sched.back().bond_counter = (uint32_t)es.d_index;
+            sched.back().bond_inv = 1;
+          }
           src = E;
         }
         // A chain that ends with a kick-only pass on a group without the probe
@@ -1767,7 +1940,7 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
         // Device-like noise (no forward layer runs ahead): the forward K-D
         // on G gives D_p K_p (input), the chain's first pass is D^* K'_1 of
         // that on G -- K'_1 K_p (input) again, formed by a K-D dual pass.
-        if (ctx->dual && sched.size() - chain0 >= 2 && chain0 >= 1) {
+        if (dual_enabled && sched.size() - chain0 >= 2 && chain0 >= 1) {
           Launch& f = sched[chain0 - 1];
           const Launch& e = sched[chain0];
           const int fs = dev_kd ? dtc::kShapeKD : dtc::kShapeKDK;
@@ -1842,12 +2015,21 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
       for (int t = std::max(0, pr->t_first); t < T; ++t) {
         const bool at_init = (t + pr->t_offset == 0);
         const double* vf = hv_f + ((size_t)b * T + t) * n_obs_f;
-        const double zj_f = at_init ? zinit : (want_z ? vf[1 + j] : vf[1]);
+        // bond noise: the forward state at t is measured before its layer's
+        // outgoing Pauli P_t, whose X content flips the sign of <Z_i>
+        const uint64_t px =
+            (rc.bond && !at_init)
+                ? bond_out_x(rc, (uint64_t)(traj_offset + g % n_traj), dtc::kStreamForward,
+                             (uint32_t)(t + pr->t_offset))
+                : 0ull;
+        const double zj_f = (at_init ? zinit : (want_z ? vf[1 + j] : vf[1])) *
+                            (((px >> j) & 1ull) ? -1.0 : 1.0);
         if (pr->want_fwd) fwd[(size_t)g * T + t] = ro_a * (fac * zinit * zj_f) + ro_b;
         if (want_z) {
           double* zo = zsite + ((size_t)g * T + t) * L;
           for (int i = 0; i < L; ++i)
-            zo[i] = at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0) : vf[1 + i];
+            zo[i] = at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0)
+                            : (((px >> i) & 1ull) ? -vf[1 + i] : vf[1 + i]);
         }
         if (want_e) {
           const double zj_e = at_init ? zinit : hv_e[((size_t)b * T + t) * 2 + 1];
@@ -1939,6 +2121,39 @@ int dtc_autocorr_device(dtc_ctx* ctx, const dtc_problem* pr, const dtc_device_no
   if (!dv) return fail(DTC_EINVAL, "null device noise");
   const dtc_noise nz{0.0, 0, 0};
   return autocorr_impl(ctx, pr, &nz, dv, seed, traj_offset, n_traj, fwd, echo, zsite);
+}
+
+int dtc_autocorr_bond(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                      const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                      int64_t traj_offset, int32_t n_traj, double* fwd, double* echo,
+                      double* zsite) {
+  if (dv) return fail(DTC_EINVAL, "bond noise together with device-like noise is not supported");
+  DTC_TRY(check_problem(pr, nz));
+  std::vector<uint32_t> thr;
+  DTC_TRY(bond_thresholds(bond, pr->L, thr));
+  if (!ctx) return fail(DTC_EINVAL, "null ctx");
+  bool any = false;
+  for (uint32_t v : thr) any = any || v != 0u;
+  // no bond, or no bond can err: exactly dtc_autocorr
+  if (!any) return autocorr_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, fwd, echo, zsite);
+  if (pr->t_offset != 0) return fail(DTC_EINVAL, "bond noise needs t_offset = 0");
+  if (ctx->prefix_periods >= 0)
+    return fail(DTC_EINVAL, "bond noise cannot run with a forward prefix in place "
+                            "(dtc_prefix_release first)");
+  return autocorr_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, fwd, echo, zsite, false,
+                       bond);
+}
+
+int dtc_bond_draws(const dtc_bond_noise* bond, int32_t L, uint64_t seed, int64_t traj,
+                   uint32_t stream, uint32_t counter, int32_t* codes) {
+  if (!bond || !codes) return fail(DTC_EINVAL, "null bond/codes");
+  if (L < 1 || L > 32) return fail(DTC_EINVAL, "L must be in [1, 32]");
+  if (traj < 0) return fail(DTC_EINVAL, "traj must be >= 0");
+  std::vector<uint32_t> thr;
+  DTC_TRY(bond_thresholds(bond, L, thr));
+  for (int b = 0; b + 1 < L; ++b)
+    codes[b] = dtc::sample_bond(seed, (uint64_t)traj, stream, counter, (uint32_t)b, thr[b]);
+  return DTC_OK;
 }
 
 int dtc_prefix_build(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,

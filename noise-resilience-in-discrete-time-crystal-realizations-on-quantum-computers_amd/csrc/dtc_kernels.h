@@ -147,6 +147,7 @@ enum KickMode {
   kKickUndo = 2,     // M = (forward M)^+                  (exact undo, same draws)
   kKickBasisX = 3,   // M = H                              (X-basis measurement, noiseless)
   kKickUndoBasisX = 4,  // M = H (forward M)^+             (undo a pending kick, then H)
+  kKickBondPauli = 5,   // M = P_0: only the outgoing Pauli of a noisy diagonal (below)
 };
 
 struct KickDesc {
@@ -156,6 +157,11 @@ struct KickDesc {
   uint32_t stream;      // RNG stream (0 forward, 1 + t echo branch at t)
   uint32_t rng_period;  // RNG period counter
   uint32_t skip;        // tile bits of the pass left unkicked (identity); 0 = none
+  // bond noise (PrepArgs::bond_thr): the layer follows the diagonal layer whose
+  // two-qubit draws are (bond_stream, bond_counter); their outgoing Pauli P_0 on
+  // each site is a right factor of the site's kick, M = P_n G_n ... P_1 G_1 P_0
+  // (kKickForward / kKickInverse), or all of it (kKickBondPauli)
+  uint32_t bond_on, bond_stream, bond_counter;
 };
 
 // Kick records.  Every noisy kick of a pass is a pure function of (pass,
@@ -227,6 +233,9 @@ struct PrepArgs {
   const uint32_t* dev_thr;
   const uint32_t* dev_thr_jump;
   const double* dev_kraus;
+  // two-qubit depolarizing noise on the bonds (null = none): per bond the
+  // threshold of sample_bond (dtc_rng.h), [L_kick - 1]
+  const uint32_t* bond_thr;
   KickRec* out;            // [n_pass][batch][kRecPerState]
 };
 
@@ -346,6 +355,30 @@ hipError_t launch_reduce(const double* partial, int n_tiles, int n_obs, int batc
 // batch, first = batch_start / n_traj][cols] (fixed summation order).
 hipError_t launch_traj_sum(const double* vals, int nb, int cols, int64_t batch_start, int n_traj,
                            double* out, hipStream_t stream);
+
+// Bond noise (dtc_bond.hip): the diagonal factor tables of one layer for every
+// state of a batch, out [batch][diag_stride] in the layout of the engine's
+// build_diag_tables (n_chunks chunk tables, then one window table per start
+// bit), with the angle signs that the layer's two-qubit Pauli draws leave after
+// they are pushed to the end of the layer.  inverse = 0: a forward layer (RZZ
+// even, RZZ odd, RZ: odd bonds and fields flip); 1: the layer of an inverse
+// period (RZ^+, RZZ^+ odd, RZZ^+ even: even bonds flip) -- the table holds the
+// signed forward factors, the pass conjugates them (PassArgs::diag_conj).
+struct BondDiagArgs {
+  double2* out;            // [batch][diag_stride]
+  const double* h;         // [n_inst][L]
+  const double* phi;       // [n_inst][L-1]
+  const uint32_t* thr;     // [L-1] sample_bond thresholds
+  int L, L_eff, n_chunks, diag_stride;
+  int batch;
+  int64_t batch_start;
+  int n_traj;
+  int64_t traj_offset;
+  uint64_t seed;
+  uint32_t stream, counter;
+  int inverse;
+};
+hipError_t launch_bond_diag(const BondDiagArgs& a, hipStream_t stream);
 
 // amplitude idx[b] of state b = 1 (after the caller zeroed the batch), in the
 // batch layout of octet_bits (state_base / octet_spread)

@@ -98,6 +98,18 @@ __device__ void build_site_kick(const PrepArgs& P, const KickDesc& K, int site, 
     m[2] = make_double2(r, 0.0); m[3] = make_double2(-r, 0.0);
     return;
   }
+  if (P.bond_thr && K.bond_on) {
+    // bond noise: the outgoing Pauli of the preceding diagonal layer on this
+    // site, (right part of bond site-1's error) (left part of bond site's), as
+    // the right factor P_0 (its phase is global)
+    if (site > 0)
+      pauli_left(m, sample_bond(P.seed, traj, K.bond_stream, K.bond_counter, (uint32_t)(site - 1),
+                                P.bond_thr[site - 1]) >> 2);
+    if (site + 1 < P.L_kick)
+      pauli_left(m, sample_bond(P.seed, traj, K.bond_stream, K.bond_counter, (uint32_t)site,
+                                P.bond_thr[site]) & 3);
+  }
+  if (K.mode == kKickBondPauli) return;
   for (int q = 0; q < P.n_sub; ++q) {
     const int qq = inv ? (P.n_sub - 1 - q) : q;
     const double2* gp = P.kick + (((int64_t)K.row * P.L_kick + site) * P.n_sub + qq) * 4;

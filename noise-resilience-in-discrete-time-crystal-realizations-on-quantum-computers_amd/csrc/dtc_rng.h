@@ -86,4 +86,24 @@ DTC_HD int sample_pauli(uint64_t seed, uint64_t traj, uint32_t stream,
   return 0;
 }
 
+// Two-qubit depolarizing draw after the RZZ (or RZZ^+) of bond `bond` in one
+// diagonal layer (include/dtc.h dtc_bond_noise; Aer's depolarizing_error(p, 2)
+// as a Pauli mixture: II with weight 1 - 15p/16, each other pair p/16).
+// (stream, counter) are those of the adjacent kick layer; word c0 has bit 31
+// set, which no kick draw has (site | sub << 16 < 2^19).  Word 0 decides
+// whether an error happens (thr = round(15p/16 * 2^32), host-computed), word 1
+// which of the 15.  Returns P_site_b + 4 * P_site_b+1 (Pauli codes as above).
+static constexpr uint32_t kBondDrawBit = 0x80000000u;
+DTC_HD int sample_bond(uint64_t seed, uint64_t traj, uint32_t stream, uint32_t counter,
+                       uint32_t bond, uint32_t thr) {
+  uint32_t x, y;
+  philox_w01(kBondDrawBit | bond, counter, stream, (uint32_t)traj, (uint32_t)seed,
+             (uint32_t)(seed >> 32) ^ (uint32_t)(traj >> 32), &x, &y);
+  if (x >= thr) return 0;
+  return 1 + (int)(((uint64_t)y * 15u) >> 32);
+}
+
+// X content (X or Y) of a Pauli code.
+DTC_HD int pauli_has_x(int code) { return code == 1 || code == 2; }
+
 }  // namespace dtc

@@ -121,6 +121,16 @@ class DeviceCalibration:
         return (np.array([float(q.get("readout_p01", 0.0)) for q in sites]),
                 np.array([float(q.get("readout_p10", 0.0)) for q in sites]))
 
+    def bond_noise(self, L: int, gates_per_rzz: int = 2) -> np.ndarray:
+        """Per-bond parameter [L-1] of the chain's bond noise (SweepSpec.bond_noise,
+        include/dtc.h dtc_bond_noise) from the calibration's two-qubit gate
+        error: an RZZ is ``gates_per_rzz`` native two-qubit gates, each a
+        depolarizing channel p2 = depolarizing_param(cz_error, 2), whose
+        composition is depolarizing with 1 - (1 - p2)^gates_per_rzz.  Host only;
+        usable with the depolarizing kick model (not with device_noise)."""
+        p2 = depolarizing_param(self.cz_error, 2)
+        return np.full(max(L - 1, 0), 1.0 - (1.0 - p2) ** gates_per_rzz)
+
     def device_noise(self, L: int, n_anc_1q: int = 6, n_anc_2q: int = 2) -> DeviceNoise:
         """Channel parameters for an L-site chain (qubits[1..L]) with the
         ancilla on qubits[0].  A kick = ``kick_sx_count`` sx pulses: error

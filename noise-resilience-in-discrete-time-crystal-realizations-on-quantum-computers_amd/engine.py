@@ -38,8 +38,21 @@ class SweepSpec:
     kick: np.ndarray | None = field(default=None, repr=False)
     init_mask_value: int | None = None   # explicit Z-basis prep (overrides initial_state)
     device: object | None = field(default=None, repr=False)  # DeviceNoise (use_fakebackend=1)
+    # depolarizing_error(p, 2) after every RZZ / RZZ^+ (include/dtc.h dtc_bond_noise):
+    # a float for every bond, an [L-1] array, or None
+    bond_noise: float | np.ndarray | None = None
 
     def __post_init__(self):
+        if self.bond_noise is not None:
+            b = np.asarray(self.bond_noise, dtype=np.float64)
+            n = max(self.L - 1, 0)
+            if b.ndim == 0:
+                b = np.full(n, float(b))
+            if b.shape != (n,):
+                raise ValueError(f"bond_noise must be a float or an [L-1] = [{n}] array")
+            if np.any(~(b >= 0.0)) or np.any(b > 16.0 / 15.0):
+                raise ValueError("bond_noise must lie in [0, 16/15]")
+            self.bond_noise = np.ascontiguousarray(b)
         self.hs = np.ascontiguousarray(np.atleast_2d(self.hs)[:, : self.L], dtype=np.float64)
         ph = np.atleast_2d(self.phis)
         self.phis = np.ascontiguousarray(ph[:, : max(self.L - 1, 0)], dtype=np.float64)
@@ -67,6 +80,10 @@ class SweepSpec:
     @property
     def p(self) -> float:
         return float(self.noise_prob) if self.use_noise else 0.0
+
+    @property
+    def has_bond_noise(self) -> bool:
+        return self.bond_noise is not None and bool(np.any(self.bond_noise > 0.0))
 
     @property
     def init_mask(self) -> int:
@@ -109,6 +126,42 @@ def energy_init_mask(L: int, initial_state: str) -> int:
                     f"out of range(0, {L}) (the reference's circ.x({i}) raises for even L)")
             m |= 1 << i
     return m
+
+
+def refuse_bond_noise(spec: SweepSpec, what: str) -> None:
+    """Bond noise exists on the autocorrelator sweep only."""
+    if getattr(spec, "has_bond_noise", False):
+        raise NotImplementedError(f"{what} does not support bond noise (SweepSpec.bond_noise); "
+                                  "only DtcEngine.autocorr does")
+
+
+def bond_struct(p_bond: np.ndarray) -> "_capi.DtcBondNoise":
+    b = _capi.DtcBondNoise()
+    b.p_bond = _capi.as_dptr(p_bond)
+    return b
+
+
+def bond_draws(p_bond, L: int, seed: int, traj: int, stream: int, counter: int) -> np.ndarray:
+    """Host only (dtc_bond_draws): the Pauli pairs of one diagonal layer of one
+    trajectory, ``codes[b] = P_site_b + 4 * P_site_b+1`` (0 I, 1 X, 2 Y, 3 Z).
+    Forward layer p: (stream, counter) = (0, p); step k of the echo at t:
+    (1 + t, k)."""
+    lib = _capi.load_library()
+    pb = np.asarray(p_bond, dtype=np.float64)
+    if pb.ndim == 0:
+        pb = np.full(max(L - 1, 0), float(pb))
+    pb = np.ascontiguousarray(pb)
+    if pb.shape != (max(L - 1, 0),):
+        raise ValueError("p_bond must be a float or an [L-1] array")
+    if pb.size == 0:
+        return np.zeros(0, dtype=np.int32)
+    codes = np.zeros(L - 1, dtype=np.int32)
+    b = bond_struct(pb)
+    _capi.check(lib.dtc_bond_draws(
+        ctypes.byref(b), ctypes.c_int32(L), ctypes.c_uint64(seed), ctypes.c_int64(traj),
+        ctypes.c_uint32(stream), ctypes.c_uint32(counter),
+        codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return codes
 
 
 class DtcEngine:
@@ -179,7 +232,16 @@ class DtcEngine:
         echo = np.zeros((n_inst, n_traj, T)) if want_echo else None
         zs = np.zeros((n_inst, n_traj, T, L)) if want_zsite else None
         pr = self._problem(spec, want_fwd, want_echo, batch, t_first)
-        if spec.device is not None:
+        if spec.has_bond_noise:
+            if spec.device is not None:
+                raise NotImplementedError("bond noise together with device-like noise")
+            nz = self._noise(spec)
+            bd = bond_struct(spec.bond_noise)
+            _capi.check(self._lib.dtc_autocorr_bond(
+                self._ctx, ctypes.byref(pr), ctypes.byref(nz), None, ctypes.byref(bd),
+                ctypes.c_uint64(seed), ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj),
+                _capi.as_dptr(fwd), _capi.as_dptr(echo), _capi.as_dptr(zs)))
+        elif spec.device is not None:
             # device-like noise (include/dtc.h dtc_device_noise); spec.noise_prob unused
             if spec.device.L != spec.L:
                 raise ValueError("device noise has a different number of sites")
@@ -204,9 +266,15 @@ class DtcEngine:
         return out
 
     # -- forward prefix cache (dtc_prefix_*; user: control.optimize_g) ------
+    @staticmethod
+    def bond_draws(p_bond, L: int, seed: int, traj: int, stream: int, counter: int):
+        """The bond-noise Pauli pairs of one diagonal layer (module ``bond_draws``)."""
+        return bond_draws(p_bond, L, seed, traj, stream, counter)
+
     def prefix_build(self, spec: SweepSpec, n_traj: int, n_periods: int,
                      seed: int = 0x5EED0001, traj_offset: int = 0):
         """Keep every trajectory's state after periods 1..n_periods on the device."""
+        refuse_bond_noise(spec, "prefix_build")
         pr = self._problem(spec)
         dv = _capi.device_struct(spec.device) if spec.device is not None else None
         _capi.check(self._lib.dtc_prefix_build(
@@ -219,6 +287,7 @@ class DtcEngine:
                           t_first: int = 0, batch: int = 0):
         """``autocorr`` continuing from the prefix (periods after it and every
         echo drawn from ``seed``); same outputs without ``zsite``."""
+        refuse_bond_noise(spec, "autocorr_prefixed")
         n_inst, T = spec.n_inst, spec.T
         fwd = np.zeros((n_inst, n_traj, T)) if want_fwd else None
         echo = np.zeros((n_inst, n_traj, T)) if want_echo else None
@@ -264,6 +333,7 @@ class DtcEngine:
         or dtc_energy_device when ``spec.device`` is set: Kraus-weighted
         expectations, read-out error not applied): ``z`` [n_inst][n_traj][T][L],
         ``zz`` [..][L-1], ``x`` [..][L]."""
+        refuse_bond_noise(spec, "energy")
         n_inst, T, L = spec.n_inst, spec.T, spec.L
         z = np.zeros((n_inst, n_traj, T, L))
         zz = np.zeros((n_inst, n_traj, T, max(L - 1, 0)))
@@ -290,6 +360,7 @@ class DtcEngine:
         trajectories on the device (dtc_energy_sums; device-like noise when
         ``spec.device`` is set): ``z`` [n_inst][T][L], ``zz`` [..][L-1], ``x``
         [..][L].  Divide by ``n_traj`` for the estimator's means."""
+        refuse_bond_noise(spec, "energy_sums")
         n_inst, T, L = spec.n_inst, spec.T, spec.L
         z = np.zeros((n_inst, T, L))
         zz = np.zeros((n_inst, T, max(L - 1, 0)))

@@ -41,7 +41,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from .engine import N_ANCILLA_NOISY_GATES, SweepSpec
+from .engine import N_ANCILLA_NOISY_GATES, SweepSpec, refuse_bond_noise
 
 
 @dataclass(frozen=True)
@@ -222,6 +222,7 @@ def sharded_forward(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
     ``world`` processes hold 2^n_global / world shards each (1 process: virtual
     ranks; 2^n_global processes: one shard each).  Returns ``zsite`` [T][L]
     (per-site <Z_i(t)>, same meaning as dtc_autocorr's) and ``norm`` [T]."""
+    refuse_bond_noise(spec, "the sharded sweep")
     L, T = spec.L, spec.T
     W = 1 << n_global
     if world not in (1, W):
@@ -543,6 +544,7 @@ def sharded_forward_pipelined(stepper, spec: SweepSpec, n_global: int, *, inst: 
     the per-period wall of the engine stream (``period_ms``) on the GPU; with
     the fused in-place kick+exchange the windows include the slice kicks and go
     to ``kick_exchange_ms`` instead (``exchange_ms`` is then empty)."""
+    refuse_bond_noise(spec, "the sharded sweep")
     return _run_rank(_pipelined_rank(stepper, spec, n_global, inst=inst, traj=traj, seed=seed,
                                      rank=rank, world=world, group=group, buffers=buffers,
                                      stats=stats, inplace=inplace,
@@ -569,6 +571,7 @@ def loopback_forward_pipelined(steppers, spec: SweepSpec, n_global: int, *, inst
     LoopbackHub (RCCL's stream semantics, device copies).  The ranks advance
     in lock step between the yields of ``_pipelined_rank``; the join sums their
     vectors.  Returns (rank 0's result, the hub's op log)."""
+    refuse_bond_noise(spec, "the sharded sweep")
     W = 1 << n_global
     if len(steppers) != W:
         raise ValueError("one stepper per rank")

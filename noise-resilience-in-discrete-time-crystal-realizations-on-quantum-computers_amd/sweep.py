@@ -120,7 +120,8 @@ def run_sweep(spec: SweepSpec, n_traj: int | None = None, shots: int | None = No
     per t with its own trajectories, ``autocorr_independent_t``)."""
     eng = engine or _default_engine()
     if n_traj is None:
-        n_traj = 1 if (spec.p == 0 and spec.device is None) else (shots or 1024)
+        noiseless = spec.p == 0 and spec.device is None and not spec.has_bond_noise
+        n_traj = 1 if noiseless else (shots or 1024)
     if independent_t:
         if want_zsite:
             raise ValueError("independent_t: per-site Z is a forward-sweep output")
@@ -181,10 +182,13 @@ def folder_name(L, noise_prob, use_fakebackend=0):
 
 
 def autocorr_csv_name(state, g, L, inst, tf, randomphi, phi_delta, phi_amplitude, noise_prob,
-                      use_noise):
-    """fast.py:266."""
+                      use_noise, bond_noise_prob=0.0):
+    """fast.py:266; with bond noise (no reference counterpart) ``_bond{p}``
+    before the extension."""
+    bond = f"_bond{bond_noise_prob}" if bond_noise_prob else ""
     return (f"autocorr_data_{state}_g{g}_L{L}_inst{inst}_tf{tf}_randomphi{randomphi}"
-            f"_delta{phi_delta}_amplitude{phi_amplitude}_noise{noise_prob}_usenoise{use_noise}.csv")
+            f"_delta{phi_delta}_amplitude{phi_amplitude}_noise{noise_prob}_usenoise{use_noise}"
+            f"{bond}.csv")
 
 
 def write_autocorr_csv(path, ts, av_autocorr, av_autocorr_echo):
