@@ -164,9 +164,13 @@ typedef struct dtc_bond_noise {
   int32_t reserved[2];
 } dtc_bond_noise;
 
-/* dtc_autocorr with the channel above after every RZZ / RZZ^+.  dv must be NULL in this
- * version (DTC_EINVAL otherwise).  bond == NULL or every p_bond == 0: exactly dtc_autocorr.
- * DTC_EINVAL also for p_bond outside [0, 16/15], prob->t_offset != 0, and a forward
+/* dtc_autocorr, or dtc_autocorr_device when dv != NULL (noise is ignored then, outputs
+ * as dtc_autocorr_device: zsite unnormalised), with the channel above after every RZZ /
+ * RZZ^+.  bond == NULL or every p_bond == 0: exactly dtc_autocorr / dtc_autocorr_device.
+ * Under dv the forward runs K-D passes (dtc_schedule_counts[2]: nothing runs ahead, no
+ * dual pass) and every echo chain keeps its trailing kick-only pass.  Relaxation during
+ * the two-qubit gate is not modelled (the channel is the depolarizing one only).
+ * DTC_EINVAL for p_bond outside [0, 16/15], prob->t_offset != 0, and a forward
  * prefix in place on the ctx (dtc_prefix_build; release it first).  Bond runs use the
  * plain chains (no light-cone end, no dual pass, DTC_SPLIT13 ignored); each diagonal
  * pass is preceded by one launch that builds its per-state factor tables (counted
@@ -180,6 +184,18 @@ int dtc_autocorr_bond(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* no
  * codes[b] = P_site_b + 4 * P_site_b+1 with 0 = I, 1 = X, 2 = Y, 3 = Z  (codes: [L-1]). */
 int dtc_bond_draws(const dtc_bond_noise* bond, int32_t L, uint64_t seed, int64_t traj,
                    uint32_t stream, uint32_t counter, int32_t* codes);
+
+/* Host only, no device, the twin of dtc_bond_draws for the kick gates: the Pauli code
+ * (0 = I, 1 = X, 2 = Y, 3 = Z) drawn after every sub-gate of one kick layer of one
+ * trajectory, pauli[site * n_sub + sub], with the thresholds of noise->p (dv == NULL) or
+ * of dv (device-like noise: noise may be NULL); under dv, jump (nullable) receives the
+ * amplitude-damping jump flag of each sub-gate (0 everywhere otherwise).  (stream,
+ * counter): forward period p (0, p), step k of the echo at t (1 + t, k); (0xFFFFFFFF, 0)
+ * gives the draws of the neel preparation's X gates (sub 0; Pauli only, no jump).  With
+ * it a gate-by-gate model can follow a noisy trajectory through inverse periods. */
+int dtc_kick_draws(const dtc_noise* noise, const dtc_device_noise* dv, int32_t L, int32_t n_sub,
+                   uint64_t seed, int64_t traj, uint32_t stream, uint32_t counter,
+                   int32_t* pauli, int32_t* jump);
 
 /* Unit-test hook: apply n_periods Floquet periods to one host state vector
  * of 2^L complex128 amplitudes (in/out).  Forward: periods first_period,
@@ -352,11 +368,29 @@ int dtc_energy_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* nois
                     const dtc_device_noise* dv, uint64_t seed, int64_t traj_offset,
                     int32_t n_traj, double* z_sum, double* zz_sum, double* x_sum);
 
+/* dtc_energy / dtc_energy_device (dv != NULL; noise ignored then) and
+ * dtc_energy_sums with dtc_bond_noise's channel after every RZZ.  The energy
+ * circuit has forward layers only: the draws of forward period p are (stream 0,
+ * counter p), p = t + t_offset (any t_offset, as in dtc_energy).  bond == NULL
+ * or every p_bond == 0: exactly the plain entry points.  The observables of
+ * time t are taken on the state before the layer's outgoing Pauli P_t (which
+ * the next kick layer absorbs): one launch per batch then negates <Z_i> where
+ * P_t has X content on i, <Z_i Z_i+1> by the product of its two sites' flips
+ * and <X_i> where P_t has Z content, on the device, before the rows are read
+ * back or summed (counted under DTC_KERNEL_REDUCE when profiling). */
+int dtc_energy_bond(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                    const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                    int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x);
+int dtc_energy_sums_bond(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                         const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                         int64_t traj_offset, int32_t n_traj, double* z_sum, double* zz_sum,
+                         double* x_sum);
+
 /* Profiling: when enabled, every kernel launch is bracketed by HIP events on
  * the ctx stream and accumulated per kernel kind. */
 #define DTC_KERNEL_LO_PASS 0   /* fused RZZ+RZ diagonal + low-site kick pass */
 #define DTC_KERNEL_HI_PASS 1   /* high-site kick pass                        */
-#define DTC_KERNEL_REDUCE 2    /* per-state observable reduction             */
+#define DTC_KERNEL_REDUCE 2    /* per-state observable reduction; bond-noise sign pass */
 #define DTC_KERNEL_INIT 3      /* preparation: bond-noise diagonal table builder */
 #define DTC_KERNEL_FINAL_PASS 4 /* last pass of an echo chain: measure, no store */
 #define DTC_KERNEL_EXCHANGE 5  /* virtual ranks' in-place slice exchange        */

@@ -51,6 +51,9 @@ EXPORTED_SYMBOLS = (
     "dtc_synchronize",
     "dtc_autocorr_bond",
     "dtc_bond_draws",
+    "dtc_kick_draws",
+    "dtc_energy_bond",
+    "dtc_energy_sums_bond",
 )
 
 KERNEL_LO_PASS = 0
@@ -62,7 +65,7 @@ KERNEL_EXCHANGE = 5
 KERNEL_NAMES = {
     KERNEL_LO_PASS: "pass_kernel<diag>  (fused RZZ+RZ diagonal + sites 0..11 kick)",
     KERNEL_HI_PASS: "pass_kernel<none>  (kick on sites >= 12)",
-    KERNEL_REDUCE: "reduce_kernel",
+    KERNEL_REDUCE: "reduce_kernel, bond_obs_sign_kernel (bond-noise signs of the energy rows)",
     KERNEL_INIT: "bond_diag_kernel (bond-noise diagonal tables per state, dtc_autocorr_bond)",
     KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split (measure only, no store)",
     KERNEL_EXCHANGE: "exchange_swap_kernel (virtual ranks' in-place slice exchange)",
@@ -263,6 +266,16 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
             P(DtcBondNoise), ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32,
             ctypes.c_uint32, P(ctypes.c_int32),
         ]
+        lib.dtc_kick_draws.argtypes = [
+            P(DtcNoise), P(DtcDeviceNoise), ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+            ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_int32),
+            P(ctypes.c_int32),
+        ]
+        lib.dtc_energy_bond.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), P(DtcDeviceNoise), P(DtcBondNoise),
+            ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, _dp, _dp, _dp,
+        ]
+        lib.dtc_energy_sums_bond.argtypes = lib.dtc_energy_bond.argtypes
         lib.dtc_plan_groups.argtypes = [ctypes.c_int32, P(ctypes.c_uint64), ctypes.c_int32]
         for name in EXPORTED_SYMBOLS:
             if name not in ("dtc_last_error", "dtc_abi_version"):

@@ -364,14 +364,14 @@ class DtcSimulator:
         if seed is None:
             seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
         cal = getattr(self.noise_model, "device_calibration", None)
-        if cal is not None and getattr(self.noise_model, "bond_error", None) is not None:
-            raise NotImplementedError("bond noise together with device-like noise")
+        bond_err = getattr(self.noise_model, "bond_error", None)
         p = 0.0 if cal is not None else _noise_p(self.noise_model)
         eng = get_engine(self.device_index)
         counts, expv = [], []
         for ci, circ in enumerate(circs):
             if cal is not None:
-                a = _run_device(eng, circ, cal, shots, seed + 7919 * (self._calls + ci))
+                a = _run_device(eng, circ, cal, shots, seed + 7919 * (self._calls + ci),
+                                bond_p=bond_err.p if bond_err is not None else 0.0)
                 rng = np.random.default_rng([seed, self._calls, ci])
                 n0 = int(rng.binomial(shots, float(np.clip((1.0 + a) / 2.0, 0.0, 1.0))))
                 c = {}
@@ -440,14 +440,17 @@ def _run_single(eng: DtcEngine, spec: SweepSpec, f: FoldedCircuit, n_traj: int, 
     return a * (1.0 - p_anc) ** f.n_anc_noisy
 
 
-def _run_device(eng: DtcEngine, circ, cal, shots: int, seed: int) -> float:
+def _run_device(eng: DtcEngine, circ, cal, shots: int, seed: int, bond_p: float = 0.0) -> float:
     """Trajectory-mean read-out expectation of one folded circuit under the
-    calibration's device-like noise (dtc_autocorr_device)."""
+    calibration's device-like noise (dtc_autocorr_device), with
+    ``depolarizing_error(bond_p, 2)`` after every RZZ / RZZ^+ when the noise
+    model carries a two-qubit error on ``["rzz"]`` (dtc_autocorr_bond)."""
     f = fold_circuit(circ, None)
     T = f.n_fwd + 1
     dev = cal.device_noise(f.L)  # every kick is a physical (noisy) gate on the device
     spec = SweepSpec(L=f.L, T=T, hs=f.hs, phis=f.phis, kick=f.kick, probe_site=f.probe,
-                     init_mask_value=f.init_mask, device=dev)
+                     init_mask_value=f.init_mask, device=dev,
+                     bond_noise=bond_p if (bond_p > 0 and f.L > 1) else None)
     out = eng.autocorr(spec, max(1, shots), seed=seed & (2**64 - 1),
                        want_fwd=not f.echo, want_echo=f.echo, t_first=T - 1)
     a = (out["echo"] if f.echo else out["fwd"])[0, :, T - 1]

@@ -47,6 +47,10 @@ def build_parser():
     p.add_argument("--bond_noise_prob", type=float, default=0.0,
                    help="depolarizing_error(p, 2) after every RZZ / RZZ^+ of the chain (0 = none; "
                         "above 0 the file name gains _bond{p})")
+    p.add_argument("--fakebackend_bond", type=int, default=0, choices=[0, 1],
+                   help="1 (with --use_fakebackend 1) = the calibration's two-qubit gate error as "
+                        "the bond noise (DeviceCalibration.bond_noise; the file name gains "
+                        "_bondcal); 0 = none")
     p.add_argument("--initial_state", type=str, default="vacuum", choices=["vacuum", "neel"])
     p.add_argument("--use_fakebackend", type=int, default=0,
                    help="1 = device-like noise (thermal relaxation + depolarizing + read-out) "
@@ -75,6 +79,22 @@ def build_parser():
     return p
 
 
+def bond_from_args(args, cal, L):
+    """(SweepSpec.bond_noise, file-name tag) of --bond_noise_prob /
+    --fakebackend_bond (``cal``: the calibration of --use_fakebackend 1, or
+    None).  Tag 0.0 = no suffix (``autocorr_csv_name``)."""
+    if args.fakebackend_bond:
+        if cal is None:
+            raise SystemExit("--fakebackend_bond 1 needs --use_fakebackend 1")
+        if args.bond_noise_prob > 0:
+            raise SystemExit("--fakebackend_bond 1 takes the bond noise from the calibration: "
+                             "do not also give --bond_noise_prob")
+        return cal.bond_noise(L), "cal"
+    if args.bond_noise_prob > 0:
+        return args.bond_noise_prob, args.bond_noise_prob
+    return None, 0.0
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     L, T = args.L, args.tf
@@ -86,13 +106,12 @@ def main(argv=None):
         device = cal.device_noise(L)
         print(f"Device-like noise from {args.device_calibration} ({cal.name})")
     hs, phis = load_disorder(L, args.inst, args.disorder_folder)
+    bond, bond_tag = bond_from_args(args, cal if args.use_fakebackend else None, L)
     spec = SweepSpec(L=L, T=T, hs=hs, phis=phis, g=args.g, polarization=args.polarization,
                      circular_frequency=args.circular_frequency,
                      initial_state=args.initial_state, noise_prob=args.noise_prob,
                      use_noise=args.use_noise, t_offset=args.t_offset, device=device,
-                     bond_noise=args.bond_noise_prob if args.bond_noise_prob > 0 else None)
-    if spec.has_bond_noise and device is not None:
-        raise SystemExit("--bond_noise_prob does not combine with --use_fakebackend 1")
+                     bond_noise=bond)
     shots = args.shots or None
     if spec.p == 0 and device is None and not spec.has_bond_noise:
         n_traj = 1
@@ -122,7 +141,7 @@ def main(argv=None):
     folder = os.path.join(args.out_dir, sw.folder_name(L, args.noise_prob, args.use_fakebackend))
     name = sw.autocorr_csv_name(args.initial_state, args.g, L, args.inst, args.tf, args.randomphi,
                                 args.phi_delta, args.phi_amplitude, args.noise_prob,
-                                args.use_noise, bond_noise_prob=args.bond_noise_prob)
+                                args.use_noise, bond_noise_prob=bond_tag)
     path = sw.write_autocorr_csv(os.path.join(folder, name), np.arange(0, T),
                                  res.av_autocorr, res.av_autocorr_echo)
     print(f"Autocorrelation data saved to {path}")

@@ -1,5 +1,6 @@
 // dtc_bond.hip — two-qubit depolarizing noise on the RZZ bonds: the per-state
-// diagonal factor tables of one diagonal layer (dtc_kernels.h BondDiagArgs).
+// diagonal factor tables of one diagonal layer (dtc_kernels.h BondDiagArgs), and
+// the signs of the outgoing Paulis on the energy observables (BondObsArgs).
 //
 // The channel after every RZZ / RZZ^+ is a Pauli mixture (dtc_rng.h
 // sample_bond).  A Pauli pushed through the rest of the diagonal layer only
@@ -97,7 +98,58 @@ __global__ __launch_bounds__(256) void bond_diag_kernel(BondDiagArgs A) {
   }
 }
 
+// The signs that the outgoing Pauli P_t of forward layer t + t_offset leaves on
+// the energy observables of time t (dtc_kernels.h BondObsArgs).  One workgroup
+// (one wave) per (state, t): the layer's L-1 pairs are drawn once into LDS as
+// four masks (X / Z content of the left and right parts), merged per site, and
+// the row's 3 L - 1 entries after the norm negated where the rule says so --
+// a few hundred bytes per row, no state traffic.
+__global__ __launch_bounds__(64) void bond_obs_sign_kernel(BondObsArgs A) {
+  __shared__ uint32_t s_m[4];  // xL, xR, zL, zR (bit b: bond b)
+  const int t = (int)(blockIdx.x % (unsigned)A.T);
+  const int b = (int)(blockIdx.x / (unsigned)A.T);
+  if (b >= A.batch || t + A.t_offset == 0) return;  // uniform per workgroup
+  const int64_t gstate = A.batch_start + b;
+  const uint64_t traj = (uint64_t)(A.traj_offset + gstate % A.n_traj);
+  const int L = A.L;
+  if (threadIdx.x < 4) s_m[threadIdx.x] = 0u;
+  __syncthreads();
+  if ((int)threadIdx.x < L - 1) {
+    const int bond = (int)threadIdx.x;
+    const int code = sample_bond(A.seed, traj, kStreamForward, (uint32_t)(t + A.t_offset),
+                                 (uint32_t)bond, A.thr[bond]);
+    if (pauli_has_x(code & 3)) atomicOr(&s_m[0], 1u << bond);
+    if (pauli_has_x(code >> 2)) atomicOr(&s_m[1], 1u << bond);
+    if (pauli_has_z(code & 3)) atomicOr(&s_m[2], 1u << bond);
+    if (pauli_has_z(code >> 2)) atomicOr(&s_m[3], 1u << bond);
+  }
+  __syncthreads();
+  // site i carries (right part of bond i-1) (left part of bond i)
+  const uint32_t site_x = (s_m[1] << 1) ^ s_m[0];
+  const uint32_t site_z = (s_m[3] << 1) ^ s_m[2];
+  double* row = A.vals + ((int64_t)b * A.T + t) * (3 * L);
+  for (int e = (int)threadIdx.x; e < 3 * L - 1; e += 64) {
+    uint32_t flip;
+    if (e < L)
+      flip = (site_x >> e) & 1u;  // Z_e
+    else if (e < 2 * L - 1)
+      flip = ((site_x >> (e - L)) ^ (site_x >> (e - L + 1))) & 1u;  // Z_i Z_i+1, i = e - L
+    else
+      flip = (site_z >> (e - (2 * L - 1))) & 1u;  // X_i, i = e - (2 L - 1)
+    if (flip) row[1 + e] = -row[1 + e];
+  }
+}
+
 }  // namespace
+
+hipError_t launch_bond_obs_sign(const BondObsArgs& a, hipStream_t stream) {
+  if (a.batch < 1 || a.L < 2 || a.L > 32 || a.T < 1 || a.t_offset < 0 || a.n_traj < 1 ||
+      !a.vals || !a.thr || (int64_t)a.batch * a.T > 0x7FFFFFFFll)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bond_obs_sign_kernel, dim3((unsigned)((int64_t)a.batch * a.T)), dim3(64), 0,
+                     stream, a);
+  return hipGetLastError();
+}
 
 hipError_t launch_bond_diag(const BondDiagArgs& a, hipStream_t stream) {
   if (a.batch < 1 || a.L < 2 || a.L > 32 || a.n_traj < 1 || !a.out || !a.h || !a.phi || !a.thr ||

@@ -787,6 +787,36 @@ int launch_bond_tables(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int 
   return DTC_OK;
 }
 
+// The signs of the outgoing Paulis on a batch's finished energy rows
+// vals[batch][T][3 L] (dtc_bond.hip bond_obs_sign_kernel), in place.
+int launch_bond_signs(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
+                      double* vals, int T) {
+  dtc::BondObsArgs B{};
+  B.vals = vals;
+  B.thr = rc.bond_thr;
+  B.L = rc.pl.L;
+  B.T = T;
+  B.t_offset = rc.prob->t_offset;
+  B.batch = batch;
+  B.batch_start = batch_start;
+  B.n_traj = rc.n_traj;
+  B.traj_offset = rc.traj_offset;
+  B.seed = rc.seed;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->prof) {
+    e0 = get_event(ctx);
+    e1 = get_event(ctx);
+    DTC_HIP(hipEventRecord(e0, ctx->stream));
+  }
+  DTC_HIP(dtc::launch_bond_obs_sign(B, ctx->stream));
+  if (ctx->prof) {
+    DTC_HIP(hipEventRecord(e1, ctx->stream));
+    ctx->pending.push_back(
+        Pending{DTC_KERNEL_REDUCE, e0, e1, 16.0 * (double)batch * T * 3 * rc.pl.L});
+  }
+  return DTC_OK;
+}
+
 int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
                  const std::vector<Launch>& L) {
 #ifdef DTC_DEV_KNOBS
@@ -1531,9 +1561,10 @@ int dtc_device_info(dtc_ctx* ctx, char* name, int32_t name_len, int32_t* n_cu,
 namespace {
 
 // Host-side tables of dtc_device_noise (see include/dtc.h for the model).
-int setup_device_noise(dtc_ctx* ctx, const dtc_problem* pr, const dtc_device_noise* dv,
-                       RunCfg& rc) {
-  const int L = pr->L;
+// thr [L][3]: Pauli thresholds of sample_device, jump [L]: its jump threshold,
+// kraus [L][3]: a0, a1, b of the weighted amplitude-damping operators.
+int device_noise_tables(const dtc_device_noise* dv, int L, std::vector<uint32_t>& thr,
+                        std::vector<uint32_t>& jump, std::vector<double>& kraus) {
   if (!dv->p_gate || !dv->t1_us || !dv->t2_us) return fail(DTC_EINVAL, "null device-noise arrays");
   if (!(dv->gate_ns >= 0.0)) return fail(DTC_EINVAL, "gate_ns must be >= 0");
   if (!(dv->readout_p01 >= 0.0 && dv->readout_p01 <= 1.0 && dv->readout_p10 >= 0.0 &&
@@ -1545,9 +1576,9 @@ int setup_device_noise(dtc_ctx* ctx, const dtc_problem* pr, const dtc_device_noi
     if (v < 0) v = 0;
     return (uint32_t)v;
   };
-  std::vector<uint32_t> jump(L);
-  std::vector<double> kraus((size_t)3 * L);
-  rc.dev_thr_host.assign((size_t)3 * L, 0u);
+  jump.assign(L, 0u);
+  kraus.assign((size_t)3 * L, 0.0);
+  thr.assign((size_t)3 * L, 0u);
   for (int i = 0; i < L; ++i) {
     const double p = dv->p_gate[i];
     if (!(p >= 0.0 && p <= 4.0 / 3.0)) return fail(DTC_EINVAL, "p_gate out of range");
@@ -1563,15 +1594,23 @@ int setup_device_noise(dtc_ctx* ctx, const dtc_problem* pr, const dtc_device_noi
     // dephasing then depolarizing(p): X, Y w.p. p/4, Z w.p. (1-d) p/4 + d (1 - 3p/4)
     const double px = p / 4.0, py = p / 4.0;
     const double pzz = (1.0 - pz_deph) * p / 4.0 + pz_deph * (1.0 - 3.0 * p / 4.0);
-    rc.dev_thr_host[3 * i + 0] = u32(px);
-    rc.dev_thr_host[3 * i + 1] = u32(px + py);
-    rc.dev_thr_host[3 * i + 2] = u32(px + py + pzz);
+    thr[3 * i + 0] = u32(px);
+    thr[3 * i + 1] = u32(px + py);
+    thr[3 * i + 2] = u32(px + py + pzz);
     const double q1 = gamma / 2.0, q0 = 1.0 - q1;
     jump[i] = u32(q1);
     kraus[3 * i + 0] = 1.0 / std::sqrt(q0);
     kraus[3 * i + 1] = std::sqrt(1.0 - gamma) / std::sqrt(q0);
     kraus[3 * i + 2] = q1 > 0.0 ? std::sqrt(gamma / q1) : 0.0;
   }
+  return DTC_OK;
+}
+
+int setup_device_noise(dtc_ctx* ctx, const dtc_problem* pr, const dtc_device_noise* dv,
+                       RunCfg& rc) {
+  std::vector<uint32_t> jump;
+  std::vector<double> kraus;
+  DTC_TRY(device_noise_tables(dv, pr->L, rc.dev_thr_host, jump, kraus));
   DTC_TRY(ensure(ctx->dev_thr, rc.dev_thr_host.size() * sizeof(uint32_t)));
   DTC_TRY(ensure(ctx->dev_jump, jump.size() * sizeof(uint32_t)));
   DTC_TRY(ensure(ctx->dev_kraus, kraus.size() * sizeof(double)));
@@ -1812,7 +1851,8 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     // never undone; if any chain does not fold, the schedule is rebuilt with
     // K-D forward passes (two passes per period, nothing run ahead).
     std::vector<Launch> sched;
-    bool dev_ahead = rc.device && ctx->dual && ctx->runahead;
+    // (with bond noise: plain chains, K-D forward passes, nothing runs ahead)
+    bool dev_ahead = rc.device && ctx->dual && ctx->runahead && !rc.bond;
     for (;;) {
     sched.clear();
     bool all_folded = true;
@@ -2127,21 +2167,58 @@ int dtc_autocorr_bond(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                       const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
                       int64_t traj_offset, int32_t n_traj, double* fwd, double* echo,
                       double* zsite) {
-  if (dv) return fail(DTC_EINVAL, "bond noise together with device-like noise is not supported");
+  // device-like noise: `noise` is ignored, as in dtc_autocorr_device
+  const dtc_noise none{0.0, 0, 0};
+  if (dv) nz = &none;
   DTC_TRY(check_problem(pr, nz));
   std::vector<uint32_t> thr;
   DTC_TRY(bond_thresholds(bond, pr->L, thr));
   if (!ctx) return fail(DTC_EINVAL, "null ctx");
   bool any = false;
   for (uint32_t v : thr) any = any || v != 0u;
-  // no bond, or no bond can err: exactly dtc_autocorr
-  if (!any) return autocorr_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, fwd, echo, zsite);
+  // no bond, or no bond can err: exactly dtc_autocorr / dtc_autocorr_device
+  if (!any) return autocorr_impl(ctx, pr, nz, dv, seed, traj_offset, n_traj, fwd, echo, zsite);
   if (pr->t_offset != 0) return fail(DTC_EINVAL, "bond noise needs t_offset = 0");
   if (ctx->prefix_periods >= 0)
     return fail(DTC_EINVAL, "bond noise cannot run with a forward prefix in place "
                             "(dtc_prefix_release first)");
-  return autocorr_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, fwd, echo, zsite, false,
-                       bond);
+  return autocorr_impl(ctx, pr, nz, dv, seed, traj_offset, n_traj, fwd, echo, zsite, false, bond);
+}
+
+int dtc_kick_draws(const dtc_noise* nz, const dtc_device_noise* dv, int32_t L, int32_t n_sub,
+                   uint64_t seed, int64_t traj, uint32_t stream, uint32_t counter, int32_t* pauli,
+                   int32_t* jump) {
+  if ((!nz && !dv) || !pauli) return fail(DTC_EINVAL, "null noise/pauli");
+  if (L < 1 || L > 32) return fail(DTC_EINVAL, "L must be in [1, 32]");
+  if (n_sub < 1 || n_sub > 8) return fail(DTC_EINVAL, "n_sub must be in [1, 8]");
+  if (traj < 0) return fail(DTC_EINVAL, "traj must be >= 0");
+  if (dv) {
+    std::vector<uint32_t> thr, thr_jump;
+    std::vector<double> kraus;
+    DTC_TRY(device_noise_tables(dv, L, thr, thr_jump, kraus));
+    // the neel preparation draws its Pauli only (init_state_mask)
+    const bool prep = stream == dtc::kStreamPrep;
+    for (int i = 0; i < L; ++i)
+      for (int q = 0; q < n_sub; ++q) {
+        int j = 0;
+        pauli[i * n_sub + q] =
+            dtc::sample_device(seed, (uint64_t)traj, stream, counter, (uint32_t)i, (uint32_t)q,
+                               thr.data() + 3 * i, prep ? 0u : thr_jump[i], &j);
+        if (jump) jump[i * n_sub + q] = j;
+      }
+    return DTC_OK;
+  }
+  if (!(nz->p >= 0.0) || nz->p > 4.0 / 3.0) return fail(DTC_EINVAL, "noise p out of range");
+  uint32_t t1, t2, t3;
+  thresholds(nz->p, &t1, &t2, &t3);
+  for (int i = 0; i < L; ++i)
+    for (int q = 0; q < n_sub; ++q) {
+      pauli[i * n_sub + q] = nz->p > 0.0 ? dtc::sample_pauli(seed, (uint64_t)traj, stream, counter,
+                                                             (uint32_t)i, (uint32_t)q, t1, t2, t3)
+                                         : 0;
+      if (jump) jump[i * n_sub + q] = 0;
+    }
+  return DTC_OK;
 }
 
 int dtc_bond_draws(const dtc_bond_noise* bond, int32_t L, uint64_t seed, int64_t traj,
@@ -2259,7 +2336,8 @@ namespace {
 // dtc_energy_sums) instead of per-trajectory rows
 int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                 const dtc_device_noise* dv, uint64_t seed, int64_t traj_offset, int32_t n_traj,
-                double* z, double* zz, double* x, bool sums = false) {
+                double* z, double* zz, double* x, bool sums = false,
+                const dtc_bond_noise* bond = nullptr) {
   if (!ctx || !z || !x || (!zz && pr && pr->L > 1)) return fail(DTC_EINVAL, "null ctx/outputs");
   DTC_TRY(check_problem(pr, nz));
   if (n_traj < 1) return fail(DTC_EINVAL, "n_traj must be >= 1");
@@ -2276,6 +2354,7 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   rc.row_kind = classify_rows(pr);
   thresholds(nz->p, &rc.thr1, &rc.thr2, &rc.thr3);
   if (dv) DTC_TRY(setup_device_noise(ctx, pr, dv, rc));
+  if (bond) DTC_TRY(setup_bond_noise(ctx, pr, bond, rc));
   const Plan& pl = rc.pl;
   const int T = pr->T, L = pr->L;
   const int P = T - 1 + pr->t_offset;
@@ -2304,6 +2383,7 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   DTC_TRY(ensure(ctx->partial, (size_t)B * pl.n_tiles * n_obs * sizeof(double)));
   DTC_TRY(ensure(ctx->vals_f, (size_t)B * T * n_v * sizeof(double)));
   DTC_TRY(ensure(ctx->basis, (size_t)B * sizeof(int64_t)));
+  if (rc.bond) DTC_TRY(ensure(ctx->bond_diag, (size_t)B * pl.diag_stride * sizeof(double2)));
   // per-instance sums: at most (B - 1) / n_traj + 2 instances per batch
   const int64_t max_inst_b = std::min<int64_t>(pr->n_inst, (B - 1) / n_traj + 2);
   if (sums) {
@@ -2332,6 +2412,22 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   // in a pass that applies D (2 passes per period); after the pass closing
   // period p the state is exactly the state at p: Z, ZZ mid-pass, then X by
   // one noiseless basis-change pass per site group (E = H^L F).
+  //
+  // Bond noise (dtc_energy_bond): every pass that applies D takes the per-state
+  // tables of forward layer d_index, and every kick layer after the first the
+  // outgoing Pauli of the layer before it.  All of the above is measured on
+  // the state before the outgoing Pauli P_t of layer t + t_offset -- mid-pass
+  // after D, before the post-kick or the next pass's pre-kick that absorbs
+  // P_t, and on the X-basis rotation of that same state -- so one sign pass
+  // over the finished rows (launch_bond_obs_sign) applies P_t to all of them.
+  auto tag_bond = [&](Chain& fw) {
+    if (!rc.bond) return;
+    for (size_t k = 1; k < fw.X.size(); ++k) {
+      fw.X[k].bond_on = 1u;
+      fw.X[k].bond_stream = dtc::kStreamForward;
+      fw.X[k].bond_counter = (uint32_t)k;
+    }
+  };
   struct EPass {
     PassSpec ps;
     int parts, t_mid, t_pre;
@@ -2343,6 +2439,7 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   if (P > 0 && dv) {
     Chain fw = forward_chain(pl, 1, P, dtc::kStreamForward);
     fw.post_after_d = false;
+    tag_bond(fw);
     while (!fw.done()) {
       EPass e{next_pass(fw), 0, -1, -1, false};
       if (e.ps.diag != dtc::kDiagNone) {
@@ -2360,6 +2457,7 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     Chain fw = forward_chain(pl, 1, P + 1, dtc::kStreamForward);
     fw.trailing_d = false;
     fw.X[P].row = P - 1;  // never observed: any valid table row
+    tag_bond(fw);
     std::vector<char> x_done((size_t)T * G, 0);
     while (!fw.done()) {
       const int nd = fw.nd;
@@ -2425,9 +2523,17 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
         DTC_HIP(dtc::launch_prep(Pp, ctx->stream));
       }
       const dtc::KickRec* recs = (const dtc::KickRec*)ctx->recs.p + (i % seg) * nb * dtc::kRecPerState;
+      const bool noisy_d = rc.bond && e.ps.diag != dtc::kDiagNone;
+      if (noisy_d) {
+        Launch l{};
+        l.bond_stream = dtc::kStreamForward;
+        l.bond_counter = (uint32_t)e.ps.d_index;
+        DTC_TRY(launch_bond_tables(ctx, rc, bs, nb, l));
+      }
       DTC_TRY(launch_pass_spec(ctx, rc, bs, nb, e.ps, F, F,
                                e.parts ? dtc::kMeasEnergy : dtc::kMeasNone, 0, n_obs, nullptr,
-                               0, recs, e.parts, e.no_store, e.basis));
+                               0, recs, e.parts, e.no_store, e.basis, 0, nullptr, nullptr,
+                               noisy_d ? (const double2*)ctx->bond_diag.p : nullptr));
       if (e.parts & dtc::kPartZ)
         DTC_TRY(launch_reduce_prof(ctx, pl.n_tiles, n_obs, nb, vals + (size_t)e.t_mid * n_v, vs,
                                    0, (e.parts & dtc::kPartXPost) ? 3 * L : 2 * L, 1));
@@ -2448,6 +2554,7 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                                    vals + (size_t)e.t_mid * n_v + 2 * L, vs, 1, L, 1));
       }
     }
+    if (rc.bond) DTC_TRY(launch_bond_signs(ctx, rc, bs, nb, vals, T));
     if (sums) {
       // the batch's rows summed per instance on the device (the rows of the
       // initial time are formed from the masks below, not read)
@@ -2544,6 +2651,41 @@ int dtc_energy_sums(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   }
   if (!nz) return fail(DTC_EINVAL, "null noise");
   return energy_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, z_sum, zz_sum, x_sum, true);
+}
+
+namespace {
+
+// The energy entry points with bond noise: dv nullable (then `noise` is used).
+int energy_bond_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                     const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                     int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x,
+                     bool sums) {
+  const dtc_noise none{0.0, 0, 0};
+  if (dv) nz = &none;
+  DTC_TRY(check_problem(pr, nz));
+  std::vector<uint32_t> thr;
+  DTC_TRY(bond_thresholds(bond, pr->L, thr));
+  bool any = false;
+  for (uint32_t v : thr) any = any || v != 0u;
+  // no bond, or no bond can err: exactly the plain entry points
+  return energy_impl(ctx, pr, nz, dv, seed, traj_offset, n_traj, z, zz, x, sums,
+                     any ? bond : nullptr);
+}
+
+}  // namespace
+
+int dtc_energy_bond(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                    const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                    int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x) {
+  return energy_bond_impl(ctx, pr, nz, dv, bond, seed, traj_offset, n_traj, z, zz, x, false);
+}
+
+int dtc_energy_sums_bond(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                         const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                         int64_t traj_offset, int32_t n_traj, double* z_sum, double* zz_sum,
+                         double* x_sum) {
+  return energy_bond_impl(ctx, pr, nz, dv, bond, seed, traj_offset, n_traj, z_sum, zz_sum, x_sum,
+                          true);
 }
 
 int32_t dtc_plan_groups(int32_t n_bits, uint64_t* masks, int32_t max_groups) {

@@ -380,6 +380,25 @@ struct BondDiagArgs {
 };
 hipError_t launch_bond_diag(const BondDiagArgs& a, hipStream_t stream);
 
+// Bond noise in the energy path (dtc_bond.hip): the observables of time t are
+// measured on the state before the outgoing Pauli P_t of forward layer
+// t + t_offset (the next kick layer absorbs it), so a batch's rows
+// vals[batch][T][3 L] (per time: norm, Z_0..Z_{L-1}, ZZ_0..ZZ_{L-2},
+// X_0..X_{L-1}) get their signs in place: Z_i flips where P_t has X content on
+// i, ZZ_i by the product of its two sites' flips, X_i where P_t has Z content.
+// Times with t + t_offset = 0 (no layer yet) are left alone.
+struct BondObsArgs {
+  double* vals;            // [batch][T][3 L]
+  const uint32_t* thr;     // [L-1] sample_bond thresholds
+  int L, T, t_offset;
+  int batch;
+  int64_t batch_start;
+  int n_traj;
+  int64_t traj_offset;
+  uint64_t seed;
+};
+hipError_t launch_bond_obs_sign(const BondObsArgs& a, hipStream_t stream);
+
 // amplitude idx[b] of state b = 1 (after the caller zeroed the batch), in the
 // batch layout of octet_bits (state_base / octet_spread)
 hipError_t launch_set_basis(double2* state, int64_t state_len, const int64_t* idx,

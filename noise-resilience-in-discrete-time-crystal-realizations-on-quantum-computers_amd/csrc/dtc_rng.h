@@ -106,4 +106,7 @@ DTC_HD int sample_bond(uint64_t seed, uint64_t traj, uint32_t stream, uint32_t c
 // X content (X or Y) of a Pauli code.
 DTC_HD int pauli_has_x(int code) { return code == 1 || code == 2; }
 
+// Z content (Y or Z) of a Pauli code.
+DTC_HD int pauli_has_z(int code) { return code == 2 || code == 3; }
+
 }  // namespace dtc

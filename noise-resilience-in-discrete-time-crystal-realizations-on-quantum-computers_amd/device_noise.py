@@ -127,7 +127,10 @@ class DeviceCalibration:
         error: an RZZ is ``gates_per_rzz`` native two-qubit gates, each a
         depolarizing channel p2 = depolarizing_param(cz_error, 2), whose
         composition is depolarizing with 1 - (1 - p2)^gates_per_rzz.  Host only;
-        usable with the depolarizing kick model (not with device_noise)."""
+        usable with the depolarizing kick model and together with
+        ``device_noise`` (``--fakebackend_bond 1`` of the CLIs), in the
+        autocorrelator and in the energy path.  Relaxation during the two-qubit
+        gate is not part of it."""
         p2 = depolarizing_param(self.cz_error, 2)
         return np.full(max(L - 1, 0), 1.0 - (1.0 - p2) ** gates_per_rzz)
 

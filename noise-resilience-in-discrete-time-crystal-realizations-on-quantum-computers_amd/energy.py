@@ -148,8 +148,11 @@ def get_instances_energy(spec: SweepSpec, n_traj: int = ESTIMATOR_SHOTS,
     mean of the engine's observables (``readout`` = per-site (p01, p10)
     applied to them, device-like noise).  <H> and the read-out map are affine
     in the observables, so the means come from the engine's on-device
-    trajectory sums (``energy_sums``, dtc_energy_sums)."""
-    sums = _engine(engine).energy_sums(spec, n_traj, seed=seed, traj_offset=traj_offset)
+    trajectory sums (``energy_sums``, dtc_energy_sums; ``energy_sums_bond``
+    when the spec carries bond noise)."""
+    eng = _engine(engine)
+    run = eng.energy_sums_bond if spec.has_bond_noise else eng.energy_sums
+    sums = run(spec, n_traj, seed=seed, traj_offset=traj_offset)
     obs = {k: v / n_traj for k, v in sums.items()}
     if readout is not None:
         obs = readout_observables(obs, *readout)
@@ -174,14 +177,19 @@ def energy_folder(L: int, variant: str = "full-ham") -> str:
     return f"energy-data_L{L}-{variant}"
 
 
-def energy_csv_name(prefix, state, g, L, inst, randomphi, delta, amplitude, noise, use_noise):
+def energy_csv_name(prefix, state, g, L, inst, randomphi, delta, amplitude, noise, use_noise,
+                    bond_noise_prob=0.0):
+    """The scripts' file names; with bond noise (no reference counterpart)
+    ``_bond{p}`` before the extension, as ``sweep.autocorr_csv_name``."""
+    bond = f"_bond{bond_noise_prob}" if bond_noise_prob else ""
     return (f"{prefix}_{state}_g{g}_L{L}_inst{inst}_randomphi{randomphi}_delta{delta}"
-            f"_amplitude{amplitude}_noise{noise}_usenoise{use_noise}.csv")
+            f"_amplitude{amplitude}_noise{noise}_usenoise{use_noise}{bond}.csv")
 
 
 def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
                initial_state="vacuum", n_traj=ESTIMATOR_SHOTS, seed=0x5EED0001,
-               hamiltonian_types=("full",), accumulate=True, engine=None, calibration=None):
+               hamiltonian_types=("full",), accumulate=True, engine=None, calibration=None,
+               bond_noise=None):
     """energy.py's main loop (:212-222): for each nprob, ``av_energy / L`` per
     Hamiltonian variant.  Returns ``{(ht, nprob): [T]}``.
 
@@ -189,13 +197,17 @@ def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
     scripts — ``NoiseModel.from_backend(FakeBrisbane())`` on the simulator,
     where the loop adds no depolarizing error (energy.py:74-78, 214-218): every
     nprob column is the device-noise run (its own shots; here its own seed),
-    with per-site read-out error."""
+    with per-site read-out error.
+
+    ``bond_noise`` (a float or an [L-1] array): ``depolarizing_error(p, 2)``
+    after every RZZ, in every column (SweepSpec.bond_noise)."""
     eff = accumulated_noise(nprobs) if accumulate else [float(p) for p in nprobs]
     res = {}
     for k, (nprob, p_eff) in enumerate(zip(nprobs, eff)):
         spec = energy_spec(L, T, hs, phis, g, initial_state,
                            noise_prob=0.0 if calibration is not None else p_eff,
-                           use_noise=1 if calibration is not None else use_noise)
+                           use_noise=1 if calibration is not None else use_noise,
+                           bond_noise=bond_noise)
         readout = None
         run_seed = seed
         if calibration is not None:
@@ -210,20 +222,22 @@ def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
 
 
 def run_energy_device(L, g, hs, phis, T, calibration, initial_state="vacuum",
-                      n_traj=ESTIMATOR_SHOTS, seed=0x5EED0001, engine=None):
+                      n_traj=ESTIMATOR_SHOTS, seed=0x5EED0001, engine=None, bond_noise=None):
     """energy-fakebrisbane.py's main loop (:226-234): ``<H>(t)`` under the
     device's noise (here: device-like noise from a calibration file, see
     device_noise.py; FakeBrisbane's own data is unavailable offline), read-out
     error on every measured site, mean over instances — NOT divided by L (the
     script saves ``np.mean(energy, axis=0)`` as is).  ``calibration=None``:
-    the script with ``--use_fakebackend 0`` (an empty NoiseModel: noiseless)."""
+    the script with ``--use_fakebackend 0`` (an empty NoiseModel: noiseless).
+    ``bond_noise``: as in ``run_energy``."""
     spec = energy_spec(L, T, hs, phis, g, initial_state, noise_prob=0.0,
-                       use_noise=1 if calibration is not None else 0)
+                       use_noise=1 if calibration is not None else 0, bond_noise=bond_noise)
     readout = None
     if calibration is not None:
         spec.device = calibration.device_noise(L)
         readout = calibration.site_readout(L)
-    per = get_instances_energy(spec, n_traj if calibration is not None else 1, ("full",), seed,
+    noisy = calibration is not None or spec.has_bond_noise
+    per = get_instances_energy(spec, n_traj if noisy else 1, ("full",), seed,
                                engine, readout=readout)["full"]
     return per.mean(axis=0)
 

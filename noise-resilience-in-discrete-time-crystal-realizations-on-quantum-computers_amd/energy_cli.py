@@ -48,6 +48,12 @@ def build_parser():
     p.add_argument("--g", type=float, default=0.97)
     p.add_argument("--noise_prob", type=float, default=0.05)
     p.add_argument("--use_noise", type=int, default=1)
+    p.add_argument("--bond_noise_prob", type=float, default=0.0,
+                   help="depolarizing_error(p, 2) after every RZZ of the chain (0 = none; above 0 "
+                        "the file names gain _bond{p})")
+    p.add_argument("--fakebackend_bond", type=int, default=0, choices=[0, 1],
+                   help="1 (with --use_fakebackend 1) = the calibration's two-qubit gate error as "
+                        "the bond noise (file names gain _bondcal); 0 = none")
     p.add_argument("--initial_state", type=str, default="vacuum", choices=["vacuum", "neel"])
     p.add_argument("--use_fakebackend", type=int, default=None,
                    help="default: 1 for --mode vs-echo / fakebrisbane, else 0 (as the scripts)")
@@ -79,26 +85,31 @@ def main(argv=None):
         cal_path = args.device_calibration or DEFAULT_CALIBRATION
         cal = DeviceCalibration.from_json(cal_path)
         print(f"Device-like noise from {cal_path} ({cal.name})")
+    from .cli import bond_from_args
+
+    bond, bond_tag = bond_from_args(args, cal, L)
+    tagged = (lambda prefix: en.energy_csv_name(prefix, *name_args, bond_noise_prob=bond_tag))
     if args.mode == "fakebrisbane":
         e = en.run_energy_device(L, args.g, hs, phis, T, cal, initial_state=args.initial_state,
-                                 n_traj=args.trajectories, seed=args.seed)
+                                 n_traj=args.trajectories, seed=args.seed,
+                                 bond_noise=bond)
         cols = {"energy_p_fakebrisbane": e}
         path = os.path.join(args.out_dir, en.energy_folder(L, "fakebrisbane"),
-                            en.energy_csv_name("energy_data", *name_args))
+                            tagged("energy_data"))
     elif args.mode == "full":
         nprobs = [0, 0.001, 0.01, 0.1]
         noisy = bool(args.use_noise)
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=int(noisy),
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal)
+                            seed=args.seed, calibration=cal, bond_noise=bond)
         cols = {f"energy_p_{p}": res[("full", p)] for p in nprobs}
         path = os.path.join(args.out_dir, en.energy_folder(L, "full-ham"),
-                            en.energy_csv_name("energy_data", *name_args))
+                            tagged("energy_data"))
     elif args.mode == "ham-comparison":
         nprobs = [args.noise_prob]
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=1,
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal,
+                            seed=args.seed, calibration=cal, bond_noise=bond,
                             hamiltonian_types=("z_only", "zz_only", "x_only", "full"))
         cols = {}
         for p in nprobs:
@@ -108,19 +119,19 @@ def main(argv=None):
             cols[f"energy_sum_p_{p}"] = res[("z_only", p)] + res[("zz_only", p)]
             cols[f"energy_full_p_{p}"] = res[("full", p)]
         path = os.path.join(args.out_dir, en.energy_folder(L, "ham-comparison"),
-                            en.energy_csv_name("energy_comparison_all", *name_args))
+                            tagged("energy_comparison_all"))
     else:
         nprobs = [0.1]
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=1,
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal,
+                            seed=args.seed, calibration=cal, bond_noise=bond,
                             hamiltonian_types=("full", "z_zz"))
         cols = {}
         for p in nprobs:
             cols[f"energy_with_x_p_{p}"] = res[("full", p)]
             cols[f"energy_without_x_p_{p}"] = res[("z_zz", p)]
         path = os.path.join(args.out_dir, en.energy_folder(L, "ham-comparison"),
-                            en.energy_csv_name("energy_comparison", *name_args))
+                            tagged("energy_comparison"))
     en.write_energy_csv(path, ts, cols)
     print(f"Energy data saved to {path}")
     if args.mode == "vs-echo":

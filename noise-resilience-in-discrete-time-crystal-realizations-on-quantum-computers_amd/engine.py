@@ -128,11 +128,14 @@ def energy_init_mask(L: int, initial_state: str) -> int:
     return m
 
 
-def refuse_bond_noise(spec: SweepSpec, what: str) -> None:
-    """Bond noise exists on the autocorrelator sweep only."""
+def refuse_bond_noise(spec: SweepSpec, what: str, instead: str | None = None) -> None:
+    """Bond noise exists on the autocorrelator sweep and the ``*_bond`` energy
+    methods only."""
     if getattr(spec, "has_bond_noise", False):
-        raise NotImplementedError(f"{what} does not support bond noise (SweepSpec.bond_noise); "
-                                  "only DtcEngine.autocorr does")
+        raise NotImplementedError(
+            f"{what} does not support bond noise (SweepSpec.bond_noise); "
+            + (f"use {instead}" if instead else
+               "only DtcEngine.autocorr, energy_bond and energy_sums_bond do"))
 
 
 def bond_struct(p_bond: np.ndarray) -> "_capi.DtcBondNoise":
@@ -162,6 +165,35 @@ def bond_draws(p_bond, L: int, seed: int, traj: int, stream: int, counter: int) 
         ctypes.c_uint32(stream), ctypes.c_uint32(counter),
         codes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
     return codes
+
+
+def kick_draws(L: int, n_sub: int, seed: int, traj: int, stream: int, counter: int,
+               p: float = 0.0, device=None):
+    """Host only (dtc_kick_draws): the Pauli code after every kick sub-gate of
+    one layer of one trajectory, ``pauli[site][sub]`` (0 I, 1 X, 2 Y, 3 Z), and
+    the amplitude-damping jump flags ``jump[site][sub]`` (all 0 without
+    ``device``).  Depolarizing noise of probability ``p``, or the device-like
+    noise of ``device`` (a DeviceNoise).  Forward period q: (stream, counter) =
+    (0, q); step k of the echo at t: (1 + t, k); the neel preparation:
+    (0xFFFFFFFF, 0), sub-gate 0."""
+    lib = _capi.load_library()
+    pauli = np.zeros((L, n_sub), dtype=np.int32)
+    jump = np.zeros((L, n_sub), dtype=np.int32)
+    nz = _capi.DtcNoise()
+    nz.p = float(p)
+    nz.n_anc = N_ANCILLA_NOISY_GATES
+    dv = None
+    if device is not None:
+        if device.L != L:
+            raise ValueError("device noise has a different number of sites")
+        dv = _capi.device_struct(device)
+    ip = ctypes.POINTER(ctypes.c_int32)
+    _capi.check(lib.dtc_kick_draws(
+        ctypes.byref(nz), ctypes.byref(dv) if dv is not None else None, ctypes.c_int32(L),
+        ctypes.c_int32(n_sub), ctypes.c_uint64(seed), ctypes.c_int64(traj),
+        ctypes.c_uint32(stream), ctypes.c_uint32(counter), pauli.ctypes.data_as(ip),
+        jump.ctypes.data_as(ip)))
+    return pauli, jump
 
 
 class DtcEngine:
@@ -218,6 +250,15 @@ class DtcEngine:
         nz.n_anc = N_ANCILLA_NOISY_GATES
         return nz
 
+    @staticmethod
+    def _device(spec: SweepSpec):
+        """dtc_device_noise of ``spec.device`` (None without one)."""
+        if spec.device is None:
+            return None
+        if spec.device.L != spec.L:
+            raise ValueError("device noise has a different number of sites")
+        return _capi.device_struct(spec.device)
+
     # -- API -------------------------------------------------------------
     def autocorr(self, spec: SweepSpec, n_traj: int, seed: int = 0x5EED0001,
                  traj_offset: int = 0, want_fwd: bool = True, want_echo: bool = True,
@@ -233,12 +274,13 @@ class DtcEngine:
         zs = np.zeros((n_inst, n_traj, T, L)) if want_zsite else None
         pr = self._problem(spec, want_fwd, want_echo, batch, t_first)
         if spec.has_bond_noise:
-            if spec.device is not None:
-                raise NotImplementedError("bond noise together with device-like noise")
+            # with spec.device: device-like kick noise plus the bond channel
+            dv = self._device(spec)
             nz = self._noise(spec)
             bd = bond_struct(spec.bond_noise)
             _capi.check(self._lib.dtc_autocorr_bond(
-                self._ctx, ctypes.byref(pr), ctypes.byref(nz), None, ctypes.byref(bd),
+                self._ctx, ctypes.byref(pr), ctypes.byref(nz),
+                ctypes.byref(dv) if dv is not None else None, ctypes.byref(bd),
                 ctypes.c_uint64(seed), ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj),
                 _capi.as_dptr(fwd), _capi.as_dptr(echo), _capi.as_dptr(zs)))
         elif spec.device is not None:
@@ -270,6 +312,13 @@ class DtcEngine:
     def bond_draws(p_bond, L: int, seed: int, traj: int, stream: int, counter: int):
         """The bond-noise Pauli pairs of one diagonal layer (module ``bond_draws``)."""
         return bond_draws(p_bond, L, seed, traj, stream, counter)
+
+    @staticmethod
+    def kick_draws(L: int, n_sub: int, seed: int, traj: int, stream: int, counter: int,
+                   p: float = 0.0, device=None):
+        """The kick sub-gates' Pauli codes and jump flags of one layer (module
+        ``kick_draws``)."""
+        return kick_draws(L, n_sub, seed, traj, stream, counter, p, device)
 
     def prefix_build(self, spec: SweepSpec, n_traj: int, n_periods: int,
                      seed: int = 0x5EED0001, traj_offset: int = 0):
@@ -333,7 +382,7 @@ class DtcEngine:
         or dtc_energy_device when ``spec.device`` is set: Kraus-weighted
         expectations, read-out error not applied): ``z`` [n_inst][n_traj][T][L],
         ``zz`` [..][L-1], ``x`` [..][L]."""
-        refuse_bond_noise(spec, "energy")
+        refuse_bond_noise(spec, "energy", "DtcEngine.energy_bond")
         n_inst, T, L = spec.n_inst, spec.T, spec.L
         z = np.zeros((n_inst, n_traj, T, L))
         zz = np.zeros((n_inst, n_traj, T, max(L - 1, 0)))
@@ -360,7 +409,7 @@ class DtcEngine:
         trajectories on the device (dtc_energy_sums; device-like noise when
         ``spec.device`` is set): ``z`` [n_inst][T][L], ``zz`` [..][L-1], ``x``
         [..][L].  Divide by ``n_traj`` for the estimator's means."""
-        refuse_bond_noise(spec, "energy_sums")
+        refuse_bond_noise(spec, "energy_sums", "DtcEngine.energy_sums_bond")
         n_inst, T, L = spec.n_inst, spec.T, spec.L
         z = np.zeros((n_inst, T, L))
         zz = np.zeros((n_inst, T, max(L - 1, 0)))
@@ -377,6 +426,38 @@ class DtcEngine:
             ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj), _capi.as_dptr(z),
             _capi.as_dptr(zz) if L > 1 else None, _capi.as_dptr(x)))
         return {"z": z, "zz": zz, "x": x}
+
+    def _energy_bond(self, fn, spec: SweepSpec, lead: tuple, n_traj: int, seed: int,
+                     traj_offset: int, batch: int):
+        T, L = spec.T, spec.L
+        z = np.zeros(lead + (T, L))
+        zz = np.zeros(lead + (T, max(L - 1, 0)))
+        x = np.zeros(lead + (T, L))
+        pr = self._problem(spec, True, False, batch, 0)
+        dv = self._device(spec)
+        bd = bond_struct(spec.bond_noise) if spec.has_bond_noise else None
+        _capi.check(fn(
+            self._ctx, ctypes.byref(pr), ctypes.byref(self._noise(spec)),
+            ctypes.byref(dv) if dv is not None else None,
+            ctypes.byref(bd) if bd is not None else None, ctypes.c_uint64(seed),
+            ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj), _capi.as_dptr(z),
+            _capi.as_dptr(zz) if L > 1 else None, _capi.as_dptr(x)))
+        return {"z": z, "zz": zz, "x": x}
+
+    def energy_bond(self, spec: SweepSpec, n_traj: int, seed: int = 0x5EED0001,
+                    traj_offset: int = 0, batch: int = 0):
+        """``energy`` with ``spec.bond_noise`` after every RZZ (dtc_energy_bond;
+        depolarizing or device-like kick noise).  Without bond noise in the spec
+        it returns ``energy``'s rows."""
+        return self._energy_bond(self._lib.dtc_energy_bond, spec, (spec.n_inst, n_traj), n_traj,
+                                 seed, traj_offset, batch)
+
+    def energy_sums_bond(self, spec: SweepSpec, n_traj: int, seed: int = 0x5EED0001,
+                         traj_offset: int = 0, batch: int = 0):
+        """``energy_sums`` with ``spec.bond_noise`` after every RZZ
+        (dtc_energy_sums_bond)."""
+        return self._energy_bond(self._lib.dtc_energy_sums_bond, spec, (spec.n_inst,), n_traj,
+                                 seed, traj_offset, batch)
 
     # -- sharded state (dtc_shard_*; driver: sharded.py) ----------------
     def shard_set_basis(self, spec: SweepSpec, shard, state_ptr: int, seed: int = 0x5EED0001,
