@@ -28,8 +28,8 @@ OBJDIR  := build/obj
 LIB     := $(PKG)/lib/libdtc_hip.so
 ORACLE  := oracle/liboracle.so
 ORACLE3 := oracle/liboracle_v3.so
-SRCS    := $(PKG)/csrc/dtc_kernels.hip $(PKG)/csrc/dtc_lightcone.hip $(PKG)/csrc/dtc_tile13.hip $(PKG)/csrc/dtc_bond.hip $(PKG)/csrc/dtc_engine.cpp
-HDRS    := $(PKG)/csrc/dtc_kernels.h $(PKG)/csrc/dtc_device.h $(PKG)/csrc/dtc_rng.h include/dtc.h
+SRCS    := $(PKG)/csrc/dtc_kernels.hip $(PKG)/csrc/dtc_lightcone.hip $(PKG)/csrc/dtc_tile13.hip $(PKG)/csrc/dtc_bond.hip $(PKG)/csrc/dtc_wavefront.hip $(PKG)/csrc/dtc_engine.cpp
+HDRS    := $(PKG)/csrc/dtc_kernels.h $(PKG)/csrc/dtc_device.h $(PKG)/csrc/dtc_rng.h $(PKG)/csrc/dtc_wavefront.h include/dtc.h
 
 all: $(LIB) $(ORACLE) $(ORACLE3)
 
@@ -54,11 +54,15 @@ $(OBJDIR)/dtc_bond.o: $(PKG)/csrc/dtc_bond.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
 
+$(OBJDIR)/dtc_wavefront.o: $(PKG)/csrc/dtc_wavefront.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
+
 $(OBJDIR)/dtc_engine.o: $(PKG)/csrc/dtc_engine.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/dtc_kernels.o $(OBJDIR)/dtc_lightcone.o $(OBJDIR)/dtc_tile13.o $(OBJDIR)/dtc_bond.o $(OBJDIR)/dtc_engine.o
+$(LIB): $(OBJDIR)/dtc_kernels.o $(OBJDIR)/dtc_lightcone.o $(OBJDIR)/dtc_tile13.o $(OBJDIR)/dtc_bond.o $(OBJDIR)/dtc_wavefront.o $(OBJDIR)/dtc_engine.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared $^ -o $@
 

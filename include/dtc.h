@@ -420,6 +420,15 @@ int dtc_lightcone_counts(dtc_ctx* ctx, int64_t* counts /* [4] */);
  * 12 / 8 split). */
 int dtc_schedule_counts(dtc_ctx* ctx, int64_t* counts /* [4] */);
 
+/* Wavefront passes launched since the engine opened: stored passes that advance
+ * an echo chain's interior by several kick layers per read and write of the
+ * state, over two tiles that share site 11 (L = 20, the 12 / 8 plan, unitary
+ * RX / RY kicks, depolarizing noise only, the octet layout; DESIGN.md section
+ * 4).  On by default; an engine opened with DTC_NO_WAVEFRONT=1 in the
+ * environment keeps the plain interior (the test switch), DTC_WAVEFRONT=2..4
+ * sets the layer cap per pass (default 4).  Booked under DTC_KERNEL_LO_PASS. */
+int dtc_wavefront_count(dtc_ctx* ctx, int64_t* count);
+
 /* Device properties for reports. */
 int dtc_device_info(dtc_ctx* ctx, char* name, int32_t name_len, int32_t* n_cu,
                     double* hbm_bytes);

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "dtc_reset_stats",
     "dtc_lightcone_counts",
     "dtc_schedule_counts",
+    "dtc_wavefront_count",
     "dtc_device_info",
     "dtc_shard_set_basis",
     "dtc_shard_step",
@@ -201,6 +202,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         lib.dtc_reset_stats.argtypes = [ctypes.c_void_p]
         lib.dtc_lightcone_counts.argtypes = [ctypes.c_void_p, P(ctypes.c_int64)]
         lib.dtc_schedule_counts.argtypes = [ctypes.c_void_p, P(ctypes.c_int64)]
+        lib.dtc_wavefront_count.argtypes = [ctypes.c_void_p, P(ctypes.c_int64)]
         lib.dtc_device_info.argtypes = [
             ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32, P(ctypes.c_int32), _dp,
         ]

@@ -30,6 +30,7 @@
 #include "../../include/dtc.h"
 #include "dtc_kernels.h"
 #include "dtc_rng.h"
+#include "dtc_wavefront.h"
 
 namespace {
 
@@ -131,6 +132,14 @@ struct dtc_ctx {
   // profiles/r6q_*; the 12 / 8 split stays the default)
   bool split13 = false;
   int64_t sched_counts[4] = {};  // dtc_schedule_counts: folds, run-ahead, rebuilt, 13 / 7
+  // Wavefront interior of the echo chains (dtc_wavefront.h, dtc_wavefront.hip):
+  // on by default (profiles/r7_wavefront_ab20.txt: C2 +5.4 %);
+  // DTC_NO_WAVEFRONT=1 keeps the plain K-D-K interior, DTC_WAVEFRONT=2..4 sets
+  // the layer cap per pass (4: the measured best)
+  bool wavefront = true;
+  int wf_cap = dtc::kWfSteps;
+  int64_t wf_launches = 0;       // dtc_wavefront_count
+  DevBuf wf_tab;                 // the partial-diagonal table sets of the current problem
   double st_ms[DTC_KERNEL_KINDS] = {};
   double st_bytes[DTC_KERNEL_KINDS] = {};
   std::vector<Pending> pending;
@@ -746,7 +755,82 @@ struct Launch {
   int bond_diag = 0;
   uint32_t bond_stream = 0, bond_counter = 0;
   int bond_inv = 0;
+  // wavefront pass (dtc_wavefront.hip): wf_steps > 0 kick steps of layers
+  // wf_kick[st] on the tile bits wf_mask[st] of tile wf_tile (0: index bits
+  // 0..11; 1: three column bits + sites 11..19), partial diagonals per wf_dmask
+  // from table set wf_set, kick family wf_kind; ps is unused
+  int wf_steps = 0, wf_tile = 0, wf_dmask = 0, wf_set = 0, wf_kind = 0;
+  uint32_t wf_mask[dtc::kWfSteps] = {};
+  KickDesc wf_kick[dtc::kWfSteps] = {};
 };
+
+// The tile geometry of the wavefront tiles (WfArgs / PassKick c, s, act) and
+// the index bit outside the tile that one of its bonds reaches.
+struct WfGeo {
+  int c, s, act, out_bit, site0;  // site0: the site of tile bit c
+};
+constexpr WfGeo kWfGeo[2] = {{dtc::kTileBits, dtc::kTileBits, 0xFFF, 12, 0}, {3, 11, 0xFF8, 10, 11}};
+constexpr int kWfSetStride = (dtc::kWfSteps + 1) * 2 * dtc::kWfTab;  // double2 per instance
+
+// The two standard record rows of a wavefront launch: row j holds steps 2 j
+// (pre) and 2 j + 1 (post), each cut to its step's tile bits.
+dtc::PassKick wf_pass_kick(const Launch& l, int j) {
+  const WfGeo& g = kWfGeo[l.wf_tile];
+  dtc::PassKick pk{};
+  for (int h = 0; h < 2; ++h) {
+    const int st = 2 * j + h;
+    KickDesc k = no_kick();
+    if (st < l.wf_steps && l.wf_mask[st]) {
+      k = l.wf_kick[st];
+      k.enabled = 1;
+      k.skip = (uint32_t)g.act & ~l.wf_mask[st];
+    }
+    (h ? pk.post : pk.pre) = k;
+  }
+  pk.kind = l.wf_kind;
+  // (tile bit k < 12 = site k for the low tile: c = 12 serves the records too)
+  pk.c = g.c;
+  pk.s = g.s;
+  pk.act = g.act;
+  pk.tb = dtc::kTileBits;
+  return pk;
+}
+
+int launch_wf(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch, const Launch& l,
+              const dtc::KickRec* recs) {
+  const WfGeo& g = kWfGeo[l.wf_tile];
+  dtc::WfArgs A{};
+  A.src = l.src;
+  A.dst = l.dst;
+  A.state_len = rc.pl.len;
+  A.L_eff = rc.pl.L_eff;
+  A.c = g.c;
+  A.s = g.s;
+  A.octet_bits = rc.octet_bits;
+  A.batch = batch;
+  A.batch_start = batch_start;
+  A.n_traj = rc.n_traj;
+  A.recs = recs;
+  A.n_steps = l.wf_steps;
+  for (int st = 0; st < dtc::kWfSteps; ++st) A.mask[st] = l.wf_mask[st];
+  A.dmask = l.wf_dmask;
+  A.tab = (const double2*)ctx->wf_tab.p + (size_t)l.wf_set * rc.prob->n_inst * kWfSetStride;
+  A.out_bit = g.out_bit;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->prof) {
+    e0 = get_event(ctx);
+    e1 = get_event(ctx);
+    DTC_HIP(hipEventRecord(e0, ctx->stream));
+  }
+  DTC_HIP(dtc::launch_wavefront(A, l.wf_kind, ctx->stream));
+  ++ctx->wf_launches;
+  if (ctx->prof) {
+    DTC_HIP(hipEventRecord(e1, ctx->stream));
+    ctx->pending.push_back(Pending{DTC_KERNEL_LO_PASS, e0, e1,
+                                   32.0 * (double)((int64_t)1 << A.L_eff) * batch});
+  }
+  return DTC_OK;
+}
 
 // The per-state diagonal tables of launch l's noisy layer, into ctx->bond_diag
 // (one buffer: the stream orders the builder after the pass that read the
@@ -838,6 +922,11 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
   ctx->pk_host.clear();
   for (size_t i = 0; i < L.size(); ++i) {
     row0[i] = ctx->pk_host.size();
+    if (L[i].wf_steps) {
+      ctx->pk_host.push_back(wf_pass_kick(L[i], 0));
+      ctx->pk_host.push_back(wf_pass_kick(L[i], 1));
+      continue;
+    }
     ctx->pk_host.push_back(pass_kick(rc, L[i].ps));
     if (L[i].dst2) ctx->pk_host.push_back(pass_kick(rc, L[i].ps2));
   }
@@ -861,6 +950,10 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
     for (size_t i = i0; i < i1; ++i) {
       const Launch& l = L[i];
       const dtc::KickRec* rec = P.out + (row0[i] - row0[i0]) * batch * dtc::kRecPerState;
+      if (l.wf_steps) {
+        DTC_TRY(launch_wf(ctx, rc, batch_start, batch, l, rec));
+        continue;
+      }
       if (l.bond_diag) DTC_TRY(launch_bond_tables(ctx, rc, batch_start, batch, l));
       DTC_TRY(launch_pass_spec(ctx, rc, batch_start, batch, l.ps, l.src, l.dst, l.meas_mode,
                                l.meas_at_end, l.n_obs, l.meas_out, l.meas_stride, rec, 0,
@@ -1437,6 +1530,11 @@ int dtc_open(int32_t device, dtc_ctx** out) {
   c->lc_wide = std::getenv("DTC_NO_LCW") == nullptr;
   c->lc_wide3 = c->lc_wide && std::getenv("DTC_NO_LCW3") == nullptr;
   c->dual = std::getenv("DTC_NO_DUAL") == nullptr;
+  if (const char* e = std::getenv("DTC_WAVEFRONT")) {
+    const int v = std::atoi(e);
+    if (v >= 2 && v <= dtc::kWfSteps) c->wf_cap = v;
+  }
+  if (std::getenv("DTC_NO_WAVEFRONT")) c->wavefront = false;
   c->runahead = std::getenv("DTC_NO_RUNAHEAD") == nullptr;
   if (const char* e = std::getenv("DTC_SPLIT13")) c->split13 = std::atoi(e) != 0;
   c->verbose = std::getenv("DTC_VERBOSE") != nullptr;
@@ -1465,6 +1563,7 @@ int dtc_close(dtc_ctx* ctx) {
   release(ctx->vals_e);
   release(ctx->diag);
   release(ctx->lc_diag);
+  release(ctx->wf_tab);
   release(ctx->red_scratch);
   if (ctx->host_f.p) (void)hipHostFree(ctx->host_f.p);
   if (ctx->host_e.p) (void)hipHostFree(ctx->host_e.p);
@@ -1524,6 +1623,12 @@ int dtc_reset_stats(dtc_ctx* ctx) {
 int dtc_lightcone_counts(dtc_ctx* ctx, int64_t* counts) {
   if (!ctx || !counts) return fail(DTC_EINVAL, "null ctx / counts");
   for (int k = 0; k < 4; ++k) counts[k] = ctx->lc_launches[k];
+  return DTC_OK;
+}
+
+int dtc_wavefront_count(dtc_ctx* ctx, int64_t* count) {
+  if (!ctx || !count) return fail(DTC_EINVAL, "null argument");
+  *count = ctx->wf_launches;
   return DTC_OK;
 }
 
@@ -1700,6 +1805,160 @@ uint64_t prefix_hash(const dtc_problem* pr, int n_periods) {
   return h;
 }
 
+// ---- wavefront interior of an echo chain ------------------------------------
+// The partial-diagonal table sets of a sweep, one per distinct (tile, factor
+// sets of the steps): [set][n_inst][step][outside bit][kWfTab] (WfArgs::tab),
+// built on the host as the schedule meets them.
+struct WfTables {
+  std::vector<std::string> keys;
+  std::vector<double> host;  // re, im pairs
+  bool dirty = false;
+};
+
+// The table set of one planned pass (conjugated factors: the echo's D^*).
+int wf_table_set(const dtc_problem* pr, const dtc::wf::Pass& ps, bool conj, WfTables& wt) {
+  const WfGeo& g = kWfGeo[ps.tile];
+  const int L = pr->L;
+  std::string key(1, (char)('0' + ps.tile));
+  key += conj ? 'c' : 'f';
+  for (const dtc::wf::Step& sp : ps.steps) {
+    key += sp.kick_mask ? '|' : '/';
+    for (const dtc::wf::Factor& f : sp.factors) {
+      key += f.bond ? 'b' : 'f';
+      key += (char)('A' + f.site);
+    }
+  }
+  for (size_t i = 0; i < wt.keys.size(); ++i)
+    if (wt.keys[i] == key) return (int)i;
+  const int set = (int)wt.keys.size();
+  wt.keys.push_back(key);
+  wt.dirty = true;
+  const size_t per_set = (size_t)pr->n_inst * kWfSetStride * 2;
+  wt.host.resize((size_t)(set + 1) * per_set);
+  double* base = wt.host.data() + (size_t)set * per_set;
+  for (size_t e = 0; e < per_set; e += 2) {
+    base[e] = 1.0;
+    base[e + 1] = 0.0;
+  }
+  auto tile_bit = [&](int site) { return site - g.site0 + (g.c == dtc::kTileBits ? 0 : g.c); };
+  auto in_tile = [&](int site) { return site >= g.site0 && tile_bit(site) < dtc::kTileBits; };
+  const double sgn = conj ? 0.5 : -0.5;
+  // kick steps first, then the trailing kick-less one: table slot st
+  int st = 0;
+  for (const dtc::wf::Step& sp : ps.steps) {
+    const int slot = sp.kick_mask ? st++ : st;
+    if (sp.factors.empty()) continue;
+    for (int in = 0; in < pr->n_inst; ++in) {
+      const double* hh = pr->h + (size_t)in * L;
+      const double* pp = pr->phi + (size_t)in * (L - 1);
+      for (int var = 0; var < 2; ++var) {
+        double* o = base + (((size_t)in * (dtc::kWfSteps + 1) + slot) * 2 + var) * dtc::kWfTab * 2;
+        const double zout = var ? -1.0 : 1.0;
+        for (int half = 0; half < 2; ++half) {
+          // half 0: index = tile bits 0..6; half 1: tile bits 6..11
+          const int bit0 = half ? 6 : 0, n_ent = half ? dtc::kWfTabB : dtc::kWfTabA;
+          for (int v = 0; v < n_ent; ++v) {
+            auto z = [&](int k) { return ((v >> (k - bit0)) & 1) ? -1.0 : 1.0; };
+            double ang = 0.0;
+            for (const dtc::wf::Factor& f : sp.factors) {
+              if (!f.bond) {
+                const int k = tile_bit(f.site);
+                if ((k <= 5) == (half == 0)) ang += hh[f.site] * z(k);
+              } else if (in_tile(f.site) && in_tile(f.site + 1)) {
+                const int k = tile_bit(f.site);
+                if ((k <= 5) == (half == 0)) ang += pp[f.site] * z(k) * z(k + 1);
+              } else {
+                const int k = tile_bit(in_tile(f.site) ? f.site : f.site + 1);
+                if ((k <= 5) == (half == 0)) ang += pp[f.site] * z(k) * zout;
+              }
+            }
+            double* e = o + ((size_t)(half ? dtc::kWfTabA : 0) + v) * 2;
+            e[0] = std::cos(sgn * ang);
+            e[1] = std::sin(sgn * ang);
+          }
+        }
+      }
+    }
+  }
+  return set;
+}
+
+// Replace the run of plain stored K-D-K launches sched[r0, r1) of an echo
+// chain -- alternating between the two site groups, launch i applying layer i
+// as its pre-kick, D^*, layer i + 1 as its post-kick -- by the planner's
+// passes over the overlapping tiles.  Leaves the schedule alone (returns
+// false) when anything about the run is not the plain pattern.
+bool wf_replace(dtc_ctx* ctx, const RunCfg& rc, std::vector<Launch>& sched, size_t r0, size_t r1,
+                WfTables& wt) {
+  const int n = (int)(r1 - r0);
+  if (n < 3) return false;
+  auto same_layer = [](const KickDesc& a, const KickDesc& b) {
+    return a.row == b.row && a.mode == b.mode && a.stream == b.stream &&
+           a.rng_period == b.rng_period;
+  };
+  std::vector<KickDesc> layer(n + 1);
+  int kind = -1;
+  for (int i = 0; i < n; ++i) {
+    const Launch& l = sched[r0 + i];
+    const PassSpec& ps = l.ps;
+    if (pass_shape(ps) != dtc::kShapeKDK || ps.lc_w0 >= 0 || ps.diag != dtc::kDiagConj ||
+        ps.pre.mode != dtc::kKickInverse || ps.post.mode != dtc::kKickInverse || ps.pre.skip ||
+        ps.post.skip || ps.pre.bond_on || ps.post.bond_on || l.meas_mode != dtc::kMeasNone ||
+        l.no_store || l.basis || l.dst2 || l.bond_diag || l.wf_steps || l.src != l.dst ||
+        ps.group != (sched[r0].ps.group ^ (i & 1)))
+      return false;
+    if (i > 0 && !same_layer(sched[r0 + i - 1].ps.post, ps.pre)) return false;
+    layer[i] = ps.pre;
+    layer[i + 1] = ps.post;
+  }
+  for (const KickDesc& k : layer) {
+    const int rk = rc.row_kind[k.row];
+    if (rk != dtc::kKindRX && rk != dtc::kKindRY) return false;
+    if (kind >= 0 && rk != kind) return false;  // one kick family per pass
+    kind = rk;
+  }
+  // planner layers 1 .. n + 1 = layer[0 .. n]; the first launch's group is the
+  // one behind at entry
+  dtc::wf::Problem p = dtc::wf::plain_span(20, 12, 1, sched[r0].ps.group != 0, n);
+  p.tiles = {dtc::wf::make_tile(0, 0, 12), dtc::wf::make_tile(3, 11, 9)};
+  p.cap = ctx->wf_cap;
+  std::vector<dtc::wf::Pass> plan;
+  if (!dtc::wf::plan(p, plan) || (int)plan.size() >= n) return false;
+  std::vector<Launch> out;
+  for (const dtc::wf::Pass& ps : plan) {
+    Launch l = sched[r0];
+    l.ps = PassSpec{ps.tile, no_kick(), no_kick(), dtc::kDiagConj, 0};
+    l.wf_tile = ps.tile;
+    l.wf_kind = kind;
+    l.wf_steps = 0;
+    l.wf_dmask = 0;
+    for (const dtc::wf::Step& sp : ps.steps) {
+      if (!sp.kick_mask) {
+        l.wf_dmask |= 1 << l.wf_steps;  // the trailing step
+        continue;
+      }
+      if (l.wf_steps >= dtc::kWfSteps) return false;
+      int m = -1;
+      for (int k = 0; k < dtc::kTileBits; ++k) {
+        if (!((sp.kick_mask >> k) & 1u)) continue;
+        if (m >= 0 && sp.layer[k] != m) return false;  // one layer per step (the kernel's records)
+        m = sp.layer[k];
+      }
+      if (m < 1 || m > n + 1) return false;
+      if (!sp.factors.empty()) l.wf_dmask |= 1 << l.wf_steps;
+      l.wf_mask[l.wf_steps] = sp.kick_mask;
+      l.wf_kick[l.wf_steps] = layer[m - 1];
+      ++l.wf_steps;
+    }
+    if (l.wf_steps < 1) return false;  // (a kick-less pass: not planned for these spans)
+    l.wf_set = wf_table_set(rc.prob, ps, true, wt);
+    out.push_back(l);
+  }
+  sched.erase(sched.begin() + (std::ptrdiff_t)r0, sched.begin() + (std::ptrdiff_t)r1);
+  sched.insert(sched.begin() + (std::ptrdiff_t)r0, out.begin(), out.end());
+  return true;
+}
+
 int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                   const dtc_device_noise* dv, uint64_t seed, int64_t traj_offset, int32_t n_traj,
                   double* fwd, double* echo, double* zsite, bool use_prefix = false,
@@ -1808,6 +2067,14 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   double* const hv_f = ctx->host_f.p;
   double* const hv_e = ctx->host_e.p;
   std::vector<int64_t> masks(B);
+  // wavefront interior of the echo chains: L = 20 in the 12 / 8 plan, unitary
+  // factored kicks, depolarizing noise only, the probe only, no prefix, the
+  // octet layout
+  bool wf_on = ctx->wavefront && L == 20 && !dv && !bond && !zsite && !use_prefix && octet > 0 &&
+               pl.groups.size() == 2 && pl.groups[0].tb == dtc::kTileBits &&
+               pl.groups[0].act == 0xFFF && pl.groups[1].c == 4 && pl.groups[1].s == 12;
+  for (int k : rc.row_kind) wf_on = wf_on && (k == dtc::kKindRX || k == dtc::kKindRY);
+  WfTables wf_tables;
 
   for (int64_t bs = 0; bs < S; bs += B) {
     const int nb = (int)std::min<int64_t>(B, S - bs);
@@ -2026,6 +2293,17 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
         } else if (must_fold) {
           all_folded = false;
         }
+        // Wavefront interior: the run of plain stored K-D-K launches between
+        // the chain's first pass (here or folded into the forward's dual pass)
+        // and its end becomes the planner's deeper passes over tiles that
+        // share site 11 (dtc_wavefront.h): fewer passes over the state
+        if (wf_on && sched.size() > chain0) {
+          const bool folded = chain0 >= 1 && sched[chain0 - 1].dst2 == E &&
+                              sched[chain0].src == E;
+          const size_t r0 = folded ? chain0 : chain0 + 1;
+          const size_t r1 = sched.size() - 1;  // the chain's end (measure-only)
+          if (r1 > r0) wf_replace(ctx, rc, sched, r0, r1, wf_tables);
+        }
       }
     }
     if (!dev_ahead || all_folded) break;
@@ -2037,6 +2315,14 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     for (const Launch& l : sched) ctx->sched_counts[0] += l.dst2 != nullptr;
     if (rc.device) ++ctx->sched_counts[dev_ahead ? 1 : 2];
     if (pl.groups[0].tb == dtc::kMaxTileBits) ++ctx->sched_counts[3];
+    if (wf_tables.dirty) {
+      // new table sets (the first batch's schedule): the stream is idle here
+      DTC_HIP(hipStreamSynchronize(ctx->stream));
+      DTC_TRY(ensure(ctx->wf_tab, wf_tables.host.size() * sizeof(double)));
+      DTC_HIP(hipMemcpy(ctx->wf_tab.p, wf_tables.host.data(),
+                        wf_tables.host.size() * sizeof(double), hipMemcpyHostToDevice));
+      wf_tables.dirty = false;
+    }
     if (!use_prefix) DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, octet));
     DTC_TRY(run_launches(ctx, rc, bs, nb, sched));
     DTC_HIP(hipMemcpyAsync(hv_f, ctx->vals_f.p, (size_t)nb * T * n_obs_f * sizeof(double),

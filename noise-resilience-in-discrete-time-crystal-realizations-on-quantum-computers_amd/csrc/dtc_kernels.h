@@ -339,6 +339,39 @@ enum LcVariant { kLcVariant8 = 0, kLcVariantWide = 1, kLcVariantWide2 = 2, kLcVa
 hipError_t launch_lightcone(const PassArgs& a, dim3 grid, int kind, hipStream_t stream,
                             int* variant);
 
+// The stored wavefront pass (dtc_wavefront.hip; planner: dtc_wavefront.h): up
+// to kWfSteps masked kick layers, a partial diagonal before each and one after
+// the last, over the tile [0, c) + [s, s + 12 - c) -- c = s = 12: index bits
+// 0..11; c = 3, s = 11: three column bits + sites 11..19.  Factored unitary
+// RX / RY kicks only.  Kick records: two consecutive standard blocks
+// ([2][batch][kRecPerState]), step 2 j + h = block j's pre (h = 0) / post (h = 1)
+// layer.  Tables: per (instance, step 0 .. kWfSteps, value of index bit
+// out_bit) kWfTabA entries over tile bits 0..6 (fields of bits 0..5, bonds up
+// to (5, 6)) then kWfTabB over bits 6..11 (the rest); out_bit = the one index
+// bit outside the tile that a bond of the tile reaches (-1: none).
+static constexpr int kWfSteps = 4;
+static constexpr int kWfTabA = 128;
+static constexpr int kWfTabB = 64;
+static constexpr int kWfTab = kWfTabA + kWfTabB;
+struct WfArgs {
+  const double2* src;
+  double2* dst;            // may alias src
+  int64_t state_len;
+  int L_eff;
+  int c, s;
+  int octet_bits;
+  int batch;
+  int64_t batch_start;
+  int n_traj;
+  const KickRec* recs;
+  int n_steps;             // kick steps, 1 .. kWfSteps
+  uint32_t mask[kWfSteps]; // tile bits kicked per step
+  int dmask;               // bit st: step st (n_steps: the trailing one) has a diagonal
+  const double2* tab;      // [n_inst][kWfSteps + 1][2][kWfTab]
+  int out_bit;
+};
+hipError_t launch_wavefront(const WfArgs& a, int kind, hipStream_t stream);
+
 // out[b * out_stride + o] = sum over tiles of partial[b][tile][o_first + o],
 // o < n_out (fixed order); accumulate: += instead of =.  Large states
 // (reduce_splits(n_tiles) > 1) sum in two stages, split sums into `scratch`

@@ -1,0 +1,195 @@
+// dtc_wavefront.hip -- the stored wavefront pass: up to kWfSteps masked kick
+// layers with partial diagonals before them over one 12-bit tile, one HBM read
+// and write of the state for all of them (planner: dtc_wavefront.h; DESIGN.md
+// section 4).  Two tiles: T1 = index bits 0..11 (sites 0..11), T2 = index bits
+// 0..2 as 128-B columns + sites 11..19; the shared site 11 lets each pass lift
+// its own sites by several layers.
+//
+// Kicks: the factored RX / RY butterflies of the plain passes in their variant
+// form, from two consecutive standard record blocks per state (steps 0, 1 =
+// the first block's pre / post layer, steps 2, 3 the second's; skipped tile
+// bits carry identity records).  Diagonals: per (instance, step) a 128-entry
+// table over tile bits 0..6 (their fields, the bonds among them) and a 64-entry
+// table over bits 6..11, staged for the workgroup's value of the one index bit
+// outside the tile that a bond reaches (a sign on the in-tile site's angle).
+// Program: the tile snakes through the register layouts, 2 -> 1 -> 0 in even
+// steps and 0 -> 1 -> 2 in odd ones, so every step costs two LDS re-layouts and
+// the diagonals are applied in layouts 2 and 0 only.  The re-layouts go through
+// a half-tile buffer (exchange_split), so three workgroups share a CU: 8.9 ms
+// per four-layer pass against 10.4 ms with the full tile at two per CU
+// (profiles/r7_wavefront_ab20.txt).
+#include <hip/hip_runtime.h>
+
+#include "dtc_device.h"
+#include "dtc_kernels.h"
+
+// Three workgroups per CU (half-tile re-layouts) or two (full-tile)
+#ifndef DTC_WF_SPLIT
+#define DTC_WF_SPLIT 1
+#endif
+
+namespace dtc {
+
+// v[r] *= fac * TA[..] * TB[..] in layout LAY (2: registers = tile bits 8..11,
+// the 0..6 table is the thread's constant; 0: registers = bits 0..3, the 6..11
+// table is)
+template <int LAY>
+__device__ __forceinline__ void wf_diag(double2 (&v)[kRegs], const double2* tab, int t,
+                                        double2 fac) {
+  static_assert(LAY == 0 || LAY == 2, "diagonals in the snake's end layouts");
+  if (LAY == 2) {
+    const double2 c = cmul(fac, tab[t & (kWfTabA - 1)]);
+    const double2* tb = tab + kWfTabA + ((t >> 6) & 3);
+#pragma unroll
+    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], cmul(c, tb[r << 2]));
+  } else {
+    const double2 c = cmul(fac, tab[kWfTabA + ((t >> 2) & 63)]);
+    const double2* ta = tab + ((t & 7) << 4);
+#pragma unroll
+    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], cmul(c, ta[r]));
+  }
+}
+
+template <int KIND, int QM0, bool SPLIT>
+__global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A) {
+  // SPLIT: the re-layouts through a half-tile buffer (real parts, then
+  // imaginary parts), so LDS allows three workgroups per CU
+  __shared__ double2 s_tile[SPLIT ? 1 : kTile];
+  __shared__ double s_half[SPLIT ? kHalfSlots : 1];
+  __shared__ double2 s_tab[(kWfSteps + 1) * kWfTab];
+
+  const int t = threadIdx.x;
+  const int og = A.octet_bits;
+  const int64_t b = og ? (((int64_t)blockIdx.y << 3) | (blockIdx.x & 7)) : (int64_t)blockIdx.y;
+  const int64_t tile = og ? (int64_t)(blockIdx.x >> 3) : (int64_t)blockIdx.x;
+  if (b >= A.batch) return;  // the padding states of a last partial octet
+  const int inst = (int)((A.batch_start + b) / A.n_traj);
+  const int n = A.n_steps;
+
+  TileMap M;
+  M.c = A.c;
+  M.s = A.s;
+  M.cmask = (1 << A.c) - 1;
+  const int mid = A.s - A.c;
+  M.tbase = ((tile & (((int64_t)1 << mid) - 1)) << A.c) | ((tile >> mid) << (A.s + kTileBits - A.c));
+
+  // the steps' tables for this workgroup's outside bit, before the tile's loads
+  const int var = A.out_bit >= 0 ? (int)((M.tbase >> A.out_bit) & 1) : 0;
+  const double2* tg = A.tab + ((int64_t)inst * (kWfSteps + 1) * 2 + var) * kWfTab;
+  double2 stage[kWfSteps + 1];
+#pragma unroll
+  for (int st = 0; st <= kWfSteps; ++st) {
+    stage[st] = make_double2(1.0, 0.0);
+    if (t < kWfTab && ((A.dmask >> st) & 1)) stage[st] = tg[st * 2 * kWfTab + t];
+  }
+
+  const int64_t sbase = state_base(b, A.state_len, og);
+  const int64_t vofs = octet_spread(M.at(ybase<2>(t)), og);
+  double2 v[kRegs];
+  {
+    const double2* src = A.src + sbase + vofs;
+#pragma unroll
+    for (int r = 0; r < kRegs; ++r) {
+      const d2v w =
+          __builtin_nontemporal_load((const d2v*)(src + octet_spread(M.rel(r << 8), og)));
+      v[r] = make_double2(w.x, w.y);
+    }
+  }
+  if (t < kWfTab) {
+#pragma unroll
+    for (int st = 0; st <= kWfSteps; ++st) s_tab[st * kWfTab + t] = stage[st];
+  }
+  __syncthreads();
+
+  // the kicks' global factor (both record blocks'), folded into the first
+  // diagonal applied
+  const RecScalar R0(A.recs + b * kRecPerState);
+  const RecScalar R1(A.recs + ((int64_t)A.batch + b) * kRecPerState);
+  double2 gf = cmul(make_double2(R0.d(kRecTotal, 0), R0.d(kRecTotal, 1)),
+                    make_double2(R1.d(kRecTotal, 0), R1.d(kRecTotal, 1)));
+  auto diag = [&](auto lay, int st) {
+    if (!((A.dmask >> st) & 1)) return;
+    wf_diag<decltype(lay)::value>(v, s_tab + st * kWfTab, t, gf);
+    gf = make_double2(1.0, 0.0);
+  };
+  auto kick = [&](auto nib, int st) {
+    constexpr int N = decltype(nib)::value;
+    if (!(A.mask[st] & (0xFu << (4 * N)))) return;
+    const RecScalar R(A.recs + ((int64_t)(st >> 1) * A.batch + b) * kRecPerState);
+    apply_nibble<N, KIND, N == 0 ? QM0 : 15>(v, R, (st & 1) * kTileBits);
+  };
+  using L0 = std::integral_constant<int, 0>;
+  using L1 = std::integral_constant<int, 1>;
+  using L2 = std::integral_constant<int, 2>;
+
+  bool in0 = false;  // the tile ended in layout 0 (an odd number of steps)
+#pragma unroll 1
+  for (int st = 0; st < n; st += 2) {
+    diag(L2{}, st);
+    kick(L2{}, st);
+    xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
+    kick(L1{}, st);
+    xch_tile<SPLIT, 1, 0>(v, s_tile, s_half, t);
+    kick(L0{}, st);
+    if (st + 1 < n) {
+      diag(L0{}, st + 1);
+      kick(L0{}, st + 1);
+      xch_tile<SPLIT, 0, 1>(v, s_tile, s_half, t);
+      kick(L1{}, st + 1);
+      xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
+      kick(L2{}, st + 1);
+    } else {
+      in0 = true;
+    }
+  }
+  // the trailing kick-less step, then back to the load / store layout
+  if (in0) {
+    diag(L0{}, n);
+    xch_tile<SPLIT, 0, 2>(v, s_tile, s_half, t);
+  } else {
+    diag(L2{}, n);
+  }
+  if (gf.x != 1.0 || gf.y != 0.0) {
+#pragma unroll
+    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], gf);
+  }
+  {
+    double2* dst = A.dst + sbase + vofs;
+#pragma unroll
+    for (int r = 0; r < kRegs; ++r) {
+      d2v x;
+      x.x = v[r].x;
+      x.y = v[r].y;
+      __builtin_nontemporal_store(x, (d2v*)(dst + octet_spread(M.rel(r << 8), og)));
+    }
+  }
+}
+
+hipError_t launch_wavefront(const WfArgs& a, int kind, hipStream_t stream) {
+  if (a.L_eff < kTileBits || a.L_eff > 32 || a.n_steps < 1 || a.n_steps > kWfSteps ||
+      a.c < 0 || a.c > kTileBits || a.s < a.c || a.s + kTileBits - a.c > a.L_eff ||
+      a.out_bit >= a.L_eff || a.batch < 1 || !a.tab || !a.recs || !a.src || !a.dst)
+    return hipErrorInvalidValue;
+  if (a.octet_bits && (a.octet_bits < 4 || a.octet_bits > a.L_eff)) return hipErrorInvalidValue;
+  // nibble 0's site bits: all four, or only bit 3 when bits 0..2 are columns
+  const bool cols3 = a.c == 3;
+  if (!cols3 && a.c != kTileBits) return hipErrorInvalidValue;
+  for (int st = 0; st < a.n_steps; ++st)
+    if (a.mask[st] >> kTileBits || (cols3 && (a.mask[st] & 7u))) return hipErrorInvalidValue;
+  const int n_tiles = 1 << (a.L_eff - kTileBits);
+  const dim3 grid = a.octet_bits ? dim3(n_tiles * 8, (a.batch + 7) / 8) : dim3(n_tiles, a.batch);
+  const dim3 block(kThreads);
+  constexpr bool kSplit = DTC_WF_SPLIT != 0;
+  if (kind == kKindRX) {
+    if (cols3) hipLaunchKernelGGL((dtc_wf_pass<kKindRX, 8, kSplit>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((dtc_wf_pass<kKindRX, 15, kSplit>), grid, block, 0, stream, a);
+  } else if (kind == kKindRY) {
+    if (cols3) hipLaunchKernelGGL((dtc_wf_pass<kKindRY, 8, kSplit>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((dtc_wf_pass<kKindRY, 15, kSplit>), grid, block, 0, stream, a);
+  } else {
+    return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace dtc

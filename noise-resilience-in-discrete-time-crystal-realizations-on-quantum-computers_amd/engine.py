@@ -583,6 +583,13 @@ class DtcEngine:
         _capi.check(self._lib.dtc_schedule_counts(self._ctx, c))
         return {"folded": c[0], "device_runahead": c[1], "device_kd": c[2], "split13": c[3]}
 
+    def wavefront_count(self):
+        """Wavefront passes launched since the engine opened
+        (dtc_wavefront_count; 0 with DTC_NO_WAVEFRONT=1)."""
+        c = ctypes.c_int64()
+        _capi.check(self._lib.dtc_wavefront_count(self._ctx, ctypes.byref(c)))
+        return int(c.value)
+
     def device_info(self):
         name = ctypes.create_string_buffer(256)
         ncu = ctypes.c_int32()
