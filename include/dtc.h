@@ -386,6 +386,36 @@ int dtc_energy_sums_bond(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise*
                          int64_t traj_offset, int32_t n_traj, double* z_sum, double* zz_sum,
                          double* x_sum);
 
+/* The energy echo (additive, ABI 12 unchanged): the energy observables of the
+ * Loschmidt echo, the circuit qc_qiskit(..., echo=True) of the energy scripts
+ * builds (...-fast-energy.py:141-153: t forward periods, then
+ * UF_subcircuit.inverse() t times) and hands to the estimator.  Outputs as
+ * dtc_energy / dtc_energy_sums; row t holds <Z_i>, <Z_i Z_i+1>, <X_i> of the
+ * state E_t = the forward state after p = t + t_offset periods taken through p
+ * inverse periods -- the state dtc_autocorr measures its echo on, drawn the
+ * same way: forward period q (stream 0, counter q), step k of the echo at t
+ * (stream 1 + t, counter k; it undoes period p - k + 1), the neel preparation
+ * as in dtc_energy.  So z[..][t][probe_site] is what dtc_autocorr's echo[..][t]
+ * is made from.  Without noise every row equals the initial state's.
+ * Row p = 0 is formed from the initial mask on the host; prob->t_first is
+ * honoured as in dtc_autocorr (chains for t < t_first are not built, their
+ * rows are 0); want_fwd / want_echo are ignored and the forward is not
+ * measured (dtc_energy gives the forward energy).  Rows are bit-identical
+ * under any batching and any split of the trajectories; the sums are reduced
+ * on the device as dtc_energy_sums' and are batch-invariant up to rounding.
+ * The schedule is dtc_autocorr's echo sweep (dual pass, wavefront interior)
+ * without the light-cone end and with every chain's trailing kick-only pass
+ * kept: the pass applying a site group's last kicks measures X of that group
+ * after them, the chain's last pass norm, Z, ZZ of all sites, and stores
+ * nothing (DTC_KERNEL_FINAL_PASS).  Depolarizing or noiseless kicks of every
+ * family dtc_energy takes; device-like noise and bond noise are not covered
+ * (there is no entry point taking them: the Python wrapper refuses). */
+int dtc_energy_echo(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise, uint64_t seed,
+                    int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x);
+int dtc_energy_echo_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                         uint64_t seed, int64_t traj_offset, int32_t n_traj, double* z_sum,
+                         double* zz_sum, double* x_sum);
+
 /* Profiling: when enabled, every kernel launch is bracketed by HIP events on
  * the ctx stream and accumulated per kernel kind. */
 #define DTC_KERNEL_LO_PASS 0   /* fused RZZ+RZ diagonal + low-site kick pass */

@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "dtc_kick_draws",
     "dtc_energy_bond",
     "dtc_energy_sums_bond",
+    "dtc_energy_echo",
+    "dtc_energy_echo_sums",
 )
 
 KERNEL_LO_PASS = 0
@@ -68,7 +70,8 @@ KERNEL_NAMES = {
     KERNEL_HI_PASS: "pass_kernel<none>  (kick on sites >= 12)",
     KERNEL_REDUCE: "reduce_kernel, bond_obs_sign_kernel (bond-noise signs of the energy rows)",
     KERNEL_INIT: "bond_diag_kernel (bond-noise diagonal tables per state, dtc_autocorr_bond)",
-    KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split (measure only, no store)",
+    KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split / the last dtc_xend_pass of an energy "
+                       "echo chain (measure only, no store)",
     KERNEL_EXCHANGE: "exchange_swap_kernel (virtual ranks' in-place slice exchange)",
 }
 
@@ -239,6 +242,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
             ctypes.c_void_p, P(DtcProblem), P(DtcNoise), ctypes.c_uint64, ctypes.c_int64,
             ctypes.c_int32, _dp, _dp, _dp,
         ]
+        lib.dtc_energy_echo.argtypes = lib.dtc_energy.argtypes
+        lib.dtc_energy_echo_sums.argtypes = lib.dtc_energy.argtypes
         lib.dtc_autocorr_device.argtypes = [
             ctypes.c_void_p, P(DtcProblem), P(DtcDeviceNoise), ctypes.c_uint64, ctypes.c_int64,
             ctypes.c_int32, _dp, _dp, _dp,

@@ -634,7 +634,9 @@ int launch_pass_spec(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int ba
     const int io = dtc::io_layout(nibs), o = 3 - io;
     const bool n0 = nibs & 1, n_o = (nibs >> o) & 1;
     const bool pre = shape == dtc::kShapeK || shape == dtc::kShapeKD || shape == dtc::kShapeKDK;
-    const int lay = meas_at_end ? io : (pre ? (n_o ? o : (n0 ? 0 : io)) : io);
+    // (an energy echo chain's last pass, kPartXEnd: at its end in layout 2)
+    const int lay = meas_at_end ? ((meas_parts & dtc::kPartXEnd) ? 2 : io)
+                                : (pre ? (n_o ? o : (n0 ? 0 : io)) : io);
     auto tile_bit = [&](int site) {
       return site < g.c ? site : ((site >= g.s && site < g.s + dtc::kTileBits - g.c) ? g.c + site - g.s : -1);
     };
@@ -762,6 +764,12 @@ struct Launch {
   int wf_steps = 0, wf_tile = 0, wf_dmask = 0, wf_set = 0, wf_kind = 0;
   uint32_t wf_mask[dtc::kWfSteps] = {};
   KickDesc wf_kick[dtc::kWfSteps] = {};
+  // an end of an energy echo chain (dtc_energy_echo; meas_mode kMeasEnergy,
+  // n_obs = 3 L): kPartXEnd -- X of the pass's sites after its last kick,
+  // accumulated into the row at energy_row + 2 L -- and, on the chain's last
+  // pass, kPartZ at the end of the pass into the row's first 2 L values
+  int meas_parts = 0;
+  double* energy_row = nullptr;
 };
 
 // The tile geometry of the wavefront tiles (WfArgs / PassKick c, s, act) and
@@ -956,10 +964,19 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
       }
       if (l.bond_diag) DTC_TRY(launch_bond_tables(ctx, rc, batch_start, batch, l));
       DTC_TRY(launch_pass_spec(ctx, rc, batch_start, batch, l.ps, l.src, l.dst, l.meas_mode,
-                               l.meas_at_end, l.n_obs, l.meas_out, l.meas_stride, rec, 0,
-                               l.no_store, l.basis, 0,
+                               l.meas_at_end, l.n_obs, l.meas_out, l.meas_stride, rec,
+                               l.meas_parts, l.no_store, l.basis, 0,
                                l.dst2 ? rec + batch * dtc::kRecPerState : nullptr, l.dst2,
                                l.bond_diag ? (const double2*)ctx->bond_diag.p : nullptr));
+      if (l.meas_parts) {
+        // the end's observables into its (zeroed) time row: Z, ZZ of all sites
+        // from the chain's last pass, X of each site from its group's end
+        const int Ls = rc.pl.L;
+        const bool zpart = (l.meas_parts & dtc::kPartZ) != 0;
+        DTC_TRY(launch_reduce_prof(ctx, rc.pl.n_tiles, l.n_obs, batch,
+                                   l.energy_row + (zpart ? 0 : 2 * Ls), l.meas_stride,
+                                   zpart ? 0 : 2 * Ls, zpart ? 3 * Ls : Ls, 1));
+      }
     }
     i0 = i1;
   }
@@ -1959,16 +1976,33 @@ bool wf_replace(dtc_ctx* ctx, const RunCfg& rc, std::vector<Launch>& sched, size
   return true;
 }
 
+// The outputs of dtc_energy_echo / dtc_energy_echo_sums (shapes of dtc_energy /
+// dtc_energy_sums): with them autocorr_impl runs its echo sweep with the
+// forward unmeasured and every chain ending in the energy measurements.
+struct EchoEnergyOut {
+  double *z, *zz, *x;
+  bool sums;
+};
+
+void energy_rows_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
+                     int nb, int t_first, double* z, double* zz, double* x);
+void energy_sums_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
+                     int nb, int n_traj, int t_first, double* z, double* zz, double* x);
+
 int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                   const dtc_device_noise* dv, uint64_t seed, int64_t traj_offset, int32_t n_traj,
                   double* fwd, double* echo, double* zsite, bool use_prefix = false,
-                  const dtc_bond_noise* bond = nullptr) {
+                  const dtc_bond_noise* bond = nullptr, const EchoEnergyOut* ee = nullptr) {
   if (!ctx) return fail(DTC_EINVAL, "null ctx");
   DTC_TRY(check_problem(pr, nz));
   if (n_traj < 1) return fail(DTC_EINVAL, "n_traj must be >= 1");
   if (traj_offset < 0) return fail(DTC_EINVAL, "traj_offset must be >= 0");
-  if (pr->want_fwd && !fwd) return fail(DTC_EINVAL, "want_fwd but fwd is null");
-  if (pr->want_echo && !echo) return fail(DTC_EINVAL, "want_echo but echo is null");
+  // (the energy echo ignores want_fwd / want_echo: the echo chains only)
+  const bool want_fwd = !ee && pr->want_fwd, want_echo = ee || pr->want_echo;
+  if (want_fwd && !fwd) return fail(DTC_EINVAL, "want_fwd but fwd is null");
+  if (!ee && want_echo && !echo) return fail(DTC_EINVAL, "want_echo but echo is null");
+  if (ee && (dv || bond || zsite || use_prefix))
+    return fail(DTC_EINVAL, "internal: the energy echo runs depolarizing or noiseless chains only");
   DTC_HIP(hipSetDevice(ctx->device));
 
   RunCfg rc;
@@ -1981,7 +2015,7 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   {
     // the 13 / 7 split where its kernels cover every pass: L = 20, unitary
     // factored kicks (RX / RY rows), the probe measurement only, no prefix
-    bool s13 = ctx->split13 && pr->L == 20 && !dv && !zsite && !use_prefix && !bond;
+    bool s13 = ctx->split13 && pr->L == 20 && !dv && !zsite && !use_prefix && !bond && !ee;
     for (int k : rc.row_kind) s13 = s13 && (k == dtc::kKindRX || k == dtc::kKindRY);
     rc.pl = make_plan(pr->L, false, s13);
   }
@@ -1992,9 +2026,12 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   const int T = pr->T, L = pr->L;
   const int P = T - 1 + pr->t_offset;
   const bool want_z = zsite != nullptr;
-  const bool want_f = pr->want_fwd || want_z;
-  const bool want_e = pr->want_echo != 0;
+  const bool want_f = want_fwd || want_z;
+  const bool want_e = want_echo;
   const int n_obs_f = want_z ? 1 + L : 2;
+  // energy echo: a chain's row is norm, Z_i | Z_i Z_i+1 | X_i (energy_impl's)
+  const int n_v = 3 * L;
+  const int n_obs_e = ee ? n_v : 2;
   const int meas_f = want_z ? dtc::kMeasSites : dtc::kMeasProbe;
   const double fac = dv ? dv->anc_factor : std::pow(1.0 - nz->p, (double)nz->n_anc);
   // read-out: measured = ro_a * a + ro_b (identity without device noise)
@@ -2055,15 +2092,26 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
 
   DTC_TRY(ensure(ctx->F, (size_t)(Bp * pl.len * 16)));
   if (want_e) DTC_TRY(ensure(ctx->E, (size_t)(Bp * pl.len * 16)));
-  const int max_obs = std::max(n_obs_f, 2);
+  const int max_obs = std::max(n_obs_f, n_obs_e);
   DTC_TRY(ensure(ctx->partial, (size_t)B * pl.n_tiles * max_obs * sizeof(double)));
   DTC_TRY(ensure(ctx->vals_f, (size_t)B * T * n_obs_f * sizeof(double)));
-  if (want_e) DTC_TRY(ensure(ctx->vals_e, (size_t)B * T * 2 * sizeof(double)));
+  if (want_e) DTC_TRY(ensure(ctx->vals_e, (size_t)B * T * n_obs_e * sizeof(double)));
+  // energy echo sums: at most (B - 1) / n_traj + 2 instances per batch, summed
+  // on the device into vals_f (the forward is not measured)
+  const int64_t max_inst_b = std::min<int64_t>(pr->n_inst, (B - 1) / n_traj + 2);
+  if (ee && ee->sums) {
+    DTC_TRY(ensure(ctx->vals_f, (size_t)max_inst_b * T * n_v * sizeof(double)));
+    const size_t n_out = (size_t)pr->n_inst * T;
+    std::fill(ee->z, ee->z + n_out * L, 0.0);
+    std::fill(ee->x, ee->x + n_out * L, 0.0);
+    if (L > 1) std::fill(ee->zz, ee->zz + n_out * (L - 1), 0.0);
+  }
   DTC_TRY(ensure(ctx->basis, (size_t)B * sizeof(int64_t)));
   if (rc.bond) DTC_TRY(ensure(ctx->bond_diag, (size_t)B * pl.diag_stride * sizeof(double2)));
 
   DTC_TRY(ensure_host(ctx->host_f, (size_t)B * T * n_obs_f));
-  if (want_e) DTC_TRY(ensure_host(ctx->host_e, (size_t)B * T * 2));
+  if (want_e)
+    DTC_TRY(ensure_host(ctx->host_e, (size_t)((ee && ee->sums) ? max_inst_b : B) * T * n_obs_e));
   double* const hv_f = ctx->host_f.p;
   double* const hv_e = ctx->host_e.p;
   std::vector<int64_t> masks(B);
@@ -2100,14 +2148,16 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     DTC_HIP(hipMemsetAsync(ctx->vals_f.p, 0, (size_t)nb * T * n_obs_f * sizeof(double),
                            ctx->stream));
     if (want_e)
-      DTC_HIP(hipMemsetAsync(ctx->vals_e.p, 0, (size_t)nb * T * 2 * sizeof(double),
+      DTC_HIP(hipMemsetAsync(ctx->vals_e.p, 0, (size_t)nb * T * n_obs_e * sizeof(double),
                              ctx->stream));
 
     // DTC_NO_LIGHTCONE=1: keep the chains' last two passes (development A/B)
     // Bond noise runs the plain chains: the cone tables are per instance, and
     // the dual fold would conjugate the forward layer's table, where the
     // chain's first D^* is a noisy layer of its own
-    const bool lc_enabled = ctx->lightcone && !rc.bond;
+    // The energy echo measures every site: no cone, and the trailing kick-only
+    // pass stays (every site's last kick matters)
+    const bool lc_enabled = ctx->lightcone && !rc.bond && !ee;
     const bool dual_enabled = ctx->dual && !rc.bond;
     // Forward chain K_1 D K_2 D ... K_P D; after each D_p: measure t = p - t_offset
     // and branch the echo at t off F.  The whole batch schedule is built first.
@@ -2118,6 +2168,9 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     // never undone; if any chain does not fold, the schedule is rebuilt with
     // K-D forward passes (two passes per period, nothing run ahead).
     std::vector<Launch> sched;
+    // energy echo: every (t, group) X and every t's Z row assigned exactly once
+    const int n_grp = (int)pl.groups.size();
+    std::vector<char> x_done(ee ? (size_t)T * n_grp : 0, 0), z_done(ee ? T : 0, 0);
     // (with bond noise: plain chains, K-D forward passes, nothing runs ahead)
     bool dev_ahead = rc.device && ctx->dual && ctx->runahead && !rc.bond;
     for (;;) {
@@ -2204,6 +2257,23 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
             es.pre.bond_counter = (uint32_t)p;
           }
           sched.push_back(Launch{es, src, E, dtc::kMeasNone, 1, 2, nullptr, (int64_t)T * 2});
+          if (ee && ec.kc[es.group] == ec.n() + 1 && (es.pre.enabled || es.post.enabled)) {
+            // the pass that applies the group's last kick layer K'_1 -- the
+            // post-kick of a K-D-K / D-K or the kick of a kick-only pass --
+            // measures X of the group's sites after it
+            const int shp = pass_shape(es);
+            const bool last_is_post = shp == dtc::kShapeKDK || shp == dtc::kShapeDK;
+            if (!(last_is_post || shp == dtc::kShapeK) || x_done[(size_t)t * n_grp + es.group])
+              return fail(DTC_EINVAL, "internal: dtc_energy_echo: a group ends in another shape");
+            x_done[(size_t)t * n_grp + es.group] = 1;
+            Launch& l = sched.back();
+            l.meas_mode = dtc::kMeasEnergy;
+            l.meas_at_end = last_is_post ? 1 : 0;  // (a kick-only pass: after its kicks, mid-pass)
+            l.n_obs = n_v;
+            l.meas_stride = (int64_t)T * n_v;
+            l.meas_parts = dtc::kPartXEnd;
+            l.energy_row = (double*)ctx->vals_e.p + (size_t)t * n_v;
+          }
           if (rc.bond && es.diag != dtc::kDiagNone) {
             sched.back().bond_diag = 1;
             sched.back().bond_stream = (uint32_t)(1 + t);
@@ -2217,7 +2287,7 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
         // (K_i^+ Z_j K_i = Z_j), so that pass is dropped and the probe is read
         // after the previous one.  Not for device-like noise: its Kraus kicks
         // are not unitary and change the trajectory weight.
-        if (!rc.device && sched.size() - chain0 >= 2) {
+        if (!rc.device && !ee && sched.size() - chain0 >= 2) {
           const Launch& l = sched.back();
           const bool kick_only = l.ps.diag == dtc::kDiagNone && !l.ps.post.enabled;
           if (kick_only && !((group_bits(pl.groups[l.ps.group]) >> pr->probe_site) & 1ull))
@@ -2232,8 +2302,17 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
         // between them, then the probe.
         if (!rc.device && lc_enabled && sched.size() - chain0 >= 2)
           lc_merge(rc, sched, chain0, pr->probe_site, ctx->lc_wide, ctx->lc_wide3);
-        sched.back().meas_mode = dtc::kMeasProbe;
-        sched.back().meas_out = (double*)ctx->vals_e.p + (size_t)t * 2;
+        if (ee) {
+          // the chain's last pass: norm, Z, ZZ of all sites after its kicks
+          Launch& l = sched.back();
+          if (!(l.meas_parts & dtc::kPartXEnd) || z_done[t])
+            return fail(DTC_EINVAL, "internal: dtc_energy_echo: the chain's last pass ends no group");
+          z_done[t] = 1;
+          l.meas_parts |= dtc::kPartZ;
+        } else {
+          sched.back().meas_mode = dtc::kMeasProbe;
+          sched.back().meas_out = (double*)ctx->vals_e.p + (size_t)t * 2;
+        }
         // the echo state is only measured: the chain's last pass reads its
         // tiles and stores nothing (the next chain starts from F again)
         sched.back().no_store = 1;
@@ -2258,7 +2337,7 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                            (f.meas_mode == dtc::kMeasNone || f.meas_mode == dtc::kMeasProbe);
           const bool eok =
               pass_shape(e.ps) == es && e.ps.lc_w0 < 0 && e.ps.group == f.ps.group &&
-              e.ps.post.enabled &&
+              e.ps.post.enabled && !e.meas_parts &&
               (dev_kd ? e.ps.post.skip == 0 && f.ps.pre.skip == 0
                       : e.ps.pre.mode == dtc::kKickUndo && e.ps.pre.skip == 0 &&
                             f.ps.post.skip == 0);
@@ -2301,7 +2380,11 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
           const bool folded = chain0 >= 1 && sched[chain0 - 1].dst2 == E &&
                               sched[chain0].src == E;
           const size_t r0 = folded ? chain0 : chain0 + 1;
-          const size_t r1 = sched.size() - 1;  // the chain's end (measure-only)
+          size_t r1 = sched.size() - 1;  // the chain's end (measure-only)
+          // (energy echo: the end is every group's last pass, the run stops
+          // before the first of them)
+          for (size_t i = chain0; ee && i < r1; ++i)
+            if (sched[i].meas_parts) r1 = i;
           if (r1 > r0) wf_replace(ctx, rc, sched, r0, r1, wf_tables);
         }
       }
@@ -2311,6 +2394,12 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     if (ctx->verbose)
       std::fprintf(stderr, "[dtc] device-noise schedule rebuilt with K-D forward passes "
                            "(an echo chain did not fold into the dual pass)\n");
+    }
+    for (int t = std::max(0, pr->t_first); ee && t < T; ++t) {
+      if (t + pr->t_offset == 0) continue;
+      bool all = z_done[t] != 0;
+      for (int g = 0; g < n_grp; ++g) all = all && x_done[(size_t)t * n_grp + g];
+      if (!all) return fail(DTC_EINVAL, "internal: dtc_energy_echo left a time row unmeasured");
     }
     for (const Launch& l : sched) ctx->sched_counts[0] += l.dst2 != nullptr;
     if (rc.device) ++ctx->sched_counts[dev_ahead ? 1 : 2];
@@ -2325,6 +2414,27 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     }
     if (!use_prefix) DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, octet));
     DTC_TRY(run_launches(ctx, rc, bs, nb, sched));
+    if (ee) {
+      // rows, or their per-instance sums (traj_sum_kernel, as dtc_energy_sums)
+      const size_t vs = (size_t)T * n_v;
+      size_t n_rows = (size_t)nb;
+      const double* rows = (const double*)ctx->vals_e.p;
+      if (ee->sums) {
+        n_rows = (size_t)((bs + nb - 1) / n_traj - bs / n_traj + 1);
+        DTC_HIP(dtc::launch_traj_sum(rows, nb, (int)vs, bs, n_traj, (double*)ctx->vals_f.p,
+                                     ctx->stream));
+        rows = (const double*)ctx->vals_f.p;
+      }
+      DTC_HIP(hipMemcpyAsync(hv_e, rows, n_rows * vs * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+      DTC_HIP(hipStreamSynchronize(ctx->stream));
+      DTC_TRY(settle_pending(ctx));
+      if (ee->sums)
+        energy_sums_out(pr, hv_e, masks.data(), bs, nb, n_traj, pr->t_first, ee->z, ee->zz, ee->x);
+      else
+        energy_rows_out(pr, hv_e, masks.data(), bs, nb, pr->t_first, ee->z, ee->zz, ee->x);
+      continue;
+    }
     DTC_HIP(hipMemcpyAsync(hv_f, ctx->vals_f.p, (size_t)nb * T * n_obs_f * sizeof(double),
                            hipMemcpyDeviceToHost, ctx->stream));
     if (want_e)
@@ -2350,7 +2460,7 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                 : 0ull;
         const double zj_f = (at_init ? zinit : (want_z ? vf[1 + j] : vf[1])) *
                             (((px >> j) & 1ull) ? -1.0 : 1.0);
-        if (pr->want_fwd) fwd[(size_t)g * T + t] = ro_a * (fac * zinit * zj_f) + ro_b;
+        if (want_fwd) fwd[(size_t)g * T + t] = ro_a * (fac * zinit * zj_f) + ro_b;
         if (want_z) {
           double* zo = zsite + ((size_t)g * T + t) * L;
           for (int i = 0; i < L; ++i)
@@ -2618,6 +2728,76 @@ int dtc_apply_periods(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, 
 
 namespace {
 
+// A batch's finished rows hv[nb][T][3 L] (norm, Z_i | Z_i Z_i+1 | X_i per time)
+// into the caller's per-trajectory arrays; the row of the initial time is
+// formed from the state's mask.  Rows before t_first (dtc_energy_echo: their
+// chains are not built) are left 0.
+void energy_rows_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
+                     int nb, int t_first, double* z, double* zz, double* x) {
+  const int T = pr->T, L = pr->L, n_v = 3 * L;
+  for (int b = 0; b < nb; ++b) {
+    const int64_t g = bs + b;
+    const uint64_t m = (uint64_t)masks[b];
+    for (int t = 0; t < T; ++t) {
+      const bool at_init = (t + pr->t_offset == 0), skip = t < t_first;
+      const double* vf = hv + ((size_t)b * T + t) * n_v;
+      const double* vx = vf + 2 * L - 1;  // X_i at vx[1 + i]
+      double* zo = z + ((size_t)g * T + t) * L;
+      double* xo = x + ((size_t)g * T + t) * L;
+      for (int i = 0; i < L; ++i) {
+        zo[i] = skip ? 0.0 : (at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0) : vf[1 + i]);
+        xo[i] = (skip || at_init) ? 0.0 : vx[1 + i];
+      }
+      if (L > 1) {
+        double* zzo = zz + ((size_t)g * T + t) * (L - 1);
+        for (int i = 0; i + 1 < L; ++i)
+          zzo[i] = skip ? 0.0
+                        : (at_init ? ((((m >> i) ^ (m >> (i + 1))) & 1ull) ? -1.0 : 1.0)
+                                   : vf[1 + L + i]);
+      }
+    }
+  }
+}
+
+// The same for the per-instance sums of a batch's rows (traj_sum_kernel),
+// hv[instances of the batch][T][3 L], added to the caller's zeroed sums.
+void energy_sums_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
+                     int nb, int n_traj, int t_first, double* z, double* zz, double* x) {
+  const int T = pr->T, L = pr->L, n_v = 3 * L;
+  const int64_t i0 = bs / n_traj, n_ib = (bs + nb - 1) / n_traj - i0 + 1;
+  for (int64_t i = 0; i < n_ib; ++i) {
+    const int64_t inst = i0 + i;
+    for (int t = t_first; t < T; ++t) {
+      if (t + pr->t_offset == 0) continue;
+      const double* vf = hv + ((size_t)i * T + t) * n_v;
+      const double* vx = vf + 2 * L - 1;
+      double* zo = z + ((size_t)inst * T + t) * L;
+      double* xo = x + ((size_t)inst * T + t) * L;
+      for (int k = 0; k < L; ++k) {
+        zo[k] += vf[1 + k];
+        xo[k] += vx[1 + k];
+      }
+      if (L > 1) {
+        double* zzo = zz + ((size_t)inst * T + t) * (L - 1);
+        for (int k = 0; k + 1 < L; ++k) zzo[k] += vf[1 + L + k];
+      }
+    }
+  }
+  if (pr->t_offset == 0 && t_first == 0) {
+    for (int b = 0; b < nb; ++b) {
+      const int64_t inst = (bs + b) / n_traj;
+      const uint64_t m = (uint64_t)masks[b];
+      double* zo = z + (size_t)inst * T * L;
+      for (int k = 0; k < L; ++k) zo[k] += ((m >> k) & 1ull) ? -1.0 : 1.0;
+      if (L > 1) {
+        double* zzo = zz + (size_t)inst * T * (L - 1);
+        for (int k = 0; k + 1 < L; ++k)
+          zzo[k] += (((m >> k) ^ (m >> (k + 1))) & 1ull) ? -1.0 : 1.0;
+      }
+    }
+  }
+}
+
 // sums: z, zz, x are per-instance sums over the trajectories ([n_inst][T][.],
 // dtc_energy_sums) instead of per-trajectory rows
 int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
@@ -2851,64 +3031,14 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                              hipMemcpyDeviceToHost, ctx->stream));
       DTC_HIP(hipStreamSynchronize(ctx->stream));
       DTC_TRY(settle_pending(ctx));
-      for (int64_t i = 0; i < n_ib; ++i) {
-        const int64_t inst = i0 + i;
-        for (int t = 0; t < T; ++t) {
-          if (t + pr->t_offset == 0) continue;
-          const double* vf = hv_f + ((size_t)i * T + t) * n_v;
-          const double* vx = vf + 2 * L - 1;
-          double* zo = z + ((size_t)inst * T + t) * L;
-          double* xo = x + ((size_t)inst * T + t) * L;
-          for (int k = 0; k < L; ++k) {
-            zo[k] += vf[1 + k];
-            xo[k] += vx[1 + k];
-          }
-          if (L > 1) {
-            double* zzo = zz + ((size_t)inst * T + t) * (L - 1);
-            for (int k = 0; k + 1 < L; ++k) zzo[k] += vf[1 + L + k];
-          }
-        }
-      }
-      if (pr->t_offset == 0) {
-        for (int b = 0; b < nb; ++b) {
-          const int64_t inst = (bs + b) / n_traj;
-          const uint64_t m = (uint64_t)masks[b];
-          double* zo = z + (size_t)inst * T * L;
-          for (int k = 0; k < L; ++k) zo[k] += ((m >> k) & 1ull) ? -1.0 : 1.0;
-          if (L > 1) {
-            double* zzo = zz + (size_t)inst * T * (L - 1);
-            for (int k = 0; k + 1 < L; ++k)
-              zzo[k] += (((m >> k) ^ (m >> (k + 1))) & 1ull) ? -1.0 : 1.0;
-          }
-        }
-      }
+      energy_sums_out(pr, hv_f, masks.data(), bs, nb, n_traj, 0, z, zz, x);
       continue;
     }
     DTC_HIP(hipMemcpyAsync(hv_f, vals, (size_t)nb * T * n_v * sizeof(double),
                            hipMemcpyDeviceToHost, ctx->stream));
     DTC_HIP(hipStreamSynchronize(ctx->stream));
     DTC_TRY(settle_pending(ctx));
-    for (int b = 0; b < nb; ++b) {
-      const int64_t g = bs + b;
-      const uint64_t m = (uint64_t)masks[b];
-      for (int t = 0; t < T; ++t) {
-        const bool at_init = (t + pr->t_offset == 0);
-        const double* vf = hv_f + ((size_t)b * T + t) * n_v;
-        const double* vx = vf + 2 * L - 1;  // X_i at vx[1 + i]
-        double* zo = z + ((size_t)g * T + t) * L;
-        double* xo = x + ((size_t)g * T + t) * L;
-        for (int i = 0; i < L; ++i) {
-          zo[i] = at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0) : vf[1 + i];
-          xo[i] = at_init ? 0.0 : vx[1 + i];
-        }
-        if (L > 1) {
-          double* zzo = zz + ((size_t)g * T + t) * (L - 1);
-          for (int i = 0; i + 1 < L; ++i)
-            zzo[i] = at_init ? ((((m >> i) ^ (m >> (i + 1))) & 1ull) ? -1.0 : 1.0)
-                             : vf[1 + L + i];
-        }
-      }
-    }
+    energy_rows_out(pr, hv_f, masks.data(), bs, nb, 0, z, zz, x);
   }
   return DTC_OK;
 }
@@ -2937,6 +3067,24 @@ int dtc_energy_sums(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   }
   if (!nz) return fail(DTC_EINVAL, "null noise");
   return energy_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, z_sum, zz_sum, x_sum, true);
+}
+
+int dtc_energy_echo(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+                    int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x) {
+  if (!ctx || !z || !x || (!zz && pr && pr->L > 1)) return fail(DTC_EINVAL, "null ctx/outputs");
+  const EchoEnergyOut ee{z, zz, x, false};
+  return autocorr_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, nullptr, nullptr, nullptr,
+                       false, nullptr, &ee);
+}
+
+int dtc_energy_echo_sums(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+                         int64_t traj_offset, int32_t n_traj, double* z_sum, double* zz_sum,
+                         double* x_sum) {
+  if (!ctx || !z_sum || !x_sum || (!zz_sum && pr && pr->L > 1))
+    return fail(DTC_EINVAL, "null ctx/outputs");
+  const EchoEnergyOut ee{z_sum, zz_sum, x_sum, true};
+  return autocorr_impl(ctx, pr, nz, nullptr, seed, traj_offset, n_traj, nullptr, nullptr, nullptr,
+                       false, nullptr, &ee);
 }
 
 namespace {

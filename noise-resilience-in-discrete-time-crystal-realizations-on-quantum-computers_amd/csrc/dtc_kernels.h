@@ -53,7 +53,12 @@ enum MeasMode {
 //   kPartXPre  X_i of the kicked sites before the pre-kick     (obs [3L, 4L))
 // Kicks on other sites commute with X_i, so both X points see the state of
 // the time the engine assigns them to (dtc_energy).
-enum MeasPart { kPartZ = 1, kPartXPost = 2, kPartXPre = 4 };
+//   kPartXEnd  X_i of the kicked sites right after the pass's last kick on
+//              them -- the post-kick of a K-D-K / D-K, the kick of a kick-only
+//              pass -- (obs [2L, 3L), n_obs = 3 L; dtc_energy_echo: the ends
+//              of an echo chain).  Not together with the two points above;
+//              with it kPartZ is taken at the end of the pass.
+enum MeasPart { kPartZ = 1, kPartXPost = 2, kPartXPre = 4, kPartXEnd = 8 };
 // Which parts a pass runs: pre-kick (K), diagonal (D), post-kick (K).
 // kShapeLC: the light-cone end of an echo chain (lc_body in dtc_kernels.hip):
 // up to kLcLayers kick layers with D between them on the 8-site window at

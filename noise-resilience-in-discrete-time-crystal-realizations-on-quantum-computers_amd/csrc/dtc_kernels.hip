@@ -664,10 +664,18 @@ struct RoundPlan {
 // group, tile bits 0..4 = global 0..4 (512-B runs), 5..11 = sites 13..19 --
 // register nibble 1 holds column bit 4 (no kick: QM 14) and sites 13..15, so
 // its diagonal is two window tables (start bits 4 and 13), see diag_in.
+// XE (the ends of an echo chain of dtc_energy_echo, dtc_xend_pass): the energy
+// measurements of a state that is complete only after the pass's last kick --
+// X of each kicked nibble right after that nibble's kick (kPartXEnd; the
+// kicks still to come act on other sites and commute with it), the Z part at
+// the end of the pass; a pass with A.no_store set stores nothing.
 template <int SHAPE, int NIBS, int KIND, int MC = 0, bool NS = false, bool SPLIT = false,
-          bool DUAL = false, int GEO = kGeoStd>
+          bool DUAL = false, int GEO = kGeoStd, bool XE = false>
 __device__ __forceinline__ void pass_body(const PassArgs& A) {
   using RP = RoundPlan<NIBS, SHAPE>;
+  static_assert(!XE || (MC == 3 && !NS && !SPLIT && !DUAL && GEO == kGeoStd &&
+                        (SHAPE == kShapeK || SHAPE == kShapeDK || SHAPE == kShapeKDK)),
+                "X after the kick: the deferred reduction, the shapes a chain's group ends in");
   static_assert(GEO == kGeoStd || (NIBS == 6 && (KIND == kKindRX || KIND == kKindRY) && MC <= 1),
                 "the 7-site column geometry: factored unitary kicks, the probe at most");
   // register bits of nibble N that hold sites
@@ -1168,6 +1176,8 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
   // per point and read after the stores' barrier as in the deferred form)
   double xpost[SPLIT ? 1 : 3][4];
   double xpre[SPLIT ? 1 : 3][4];
+  // X after a nibble's last kick (XE): deferred like the two above
+  double xend[XE ? 3 : 1][4];
   // (three per CU: each X point's four per-thread sums are reduced over lane
   // bits 5, 4 (permlane swaps) and 3 (one DPP row rotation) only, and the
   // eight partials per site left in lanes 0..7 of each 16 go to LDS (s_xpart);
@@ -1212,8 +1222,15 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
     for (int q = 0; q < 4; ++q) w2 *= R.d(rec0 + 4 * N + q, 2);
     return w2;
   };
-  const bool x_pre = MC == 3 && (A.meas_parts & kPartXPre);
-  const bool x_post = MC == 3 && (A.meas_parts & kPartXPost);
+  const bool x_pre = MC == 3 && !XE && (A.meas_parts & kPartXPre);
+  const bool x_post = MC == 3 && !XE && (A.meas_parts & kPartXPost);
+  const bool x_end = XE && (A.meas_parts & kPartXEnd);
+  // (a sum taken after nibble N's factored kicks carries their share of the
+  // global factor too: scale sc * nib_w2(N))
+  auto measure_x_end = [&](auto lay_tag, double scale) {
+    constexpr int LAY = decltype(lay_tag)::value;
+    if constexpr (XE) pair_sums(lay_tag, xend[LAY], scale);
+  };
   // device-like noise: a kick layer's deferred Kraus factors (SiteMat),
   // prod over the tile bits k of rho_{k, x_k}, in layout LAY: the lane
   // nibbles' factors from the staged nibble tables (one LDS read each), times
@@ -1246,17 +1263,32 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
       if (x_pre) measure_x_pre(LIO{}, sc);
       apply_nibble<RP::IO, KIND, qm(RP::IO), FR>(v, R, 0);
       if (x_pre) sc *= nib_w2(RP::IO, 0);
+      if constexpr (XE && SHAPE == kShapeK) {
+        if (x_end) {
+          sc *= nib_w2(RP::IO, 0);
+          measure_x_end(LIO{}, sc);
+        }
+      }
     }
     if constexpr (RP::n0) {
       xch_f(LIO{}, L0{}, RP::xA);
       if (x_pre) measure_x_pre(L0{}, sc);
       apply_nibble<0, KIND, qm(0), FR>(v, R, 0);
       if (x_pre) sc *= nib_w2(0, 0);
+      if constexpr (XE && SHAPE == kShapeK) {
+        if (x_end) {
+          sc *= nib_w2(0, 0);
+          measure_x_end(L0{}, sc);
+        }
+      }
     }
     if constexpr (RP::nO) {
       xch_f(std::integral_constant<int, RP::n0 ? 0 : RP::IO>{}, LO{}, RP::xB);
       if (x_pre) measure_x_pre(LO{}, sc);
       apply_nibble<RP::O, KIND, qm(RP::O), FR>(v, R, 0);
+      if constexpr (XE && SHAPE == kShapeK) {
+        if (x_end) measure_x_end(LO{}, sc * nib_w2(RP::O, 0));
+      }
     }
   }
   DTC_TS(3);
@@ -1376,17 +1408,32 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
       if (x_post) measure_x_post(LO{}, sc);
       apply_nibble<RP::O, KIND, qm(RP::O), FR>(v, R, kTileBits);
       if (x_post) sc *= nib_w2(RP::O, kTileBits);
+      if constexpr (XE) {
+        if (x_end) {
+          sc *= nib_w2(RP::O, kTileBits);
+          measure_x_end(LO{}, sc);
+        }
+      }
     }
     if constexpr (RP::n0) {
       xch_f(std::integral_constant<int, RP::pO>{}, std::integral_constant<int, 0>{}, RP::x2);
       if (x_post) measure_x_post(L0{}, sc);
       apply_nibble<0, KIND, qm(0), FR>(v, R, kTileBits);
       if (x_post) sc *= nib_w2(0, kTileBits);
+      if constexpr (XE) {
+        if (x_end) {
+          sc *= nib_w2(0, kTileBits);
+          measure_x_end(L0{}, sc);
+        }
+      }
     }
     if constexpr (RP::nIO) {
       xch_f(std::integral_constant<int, RP::p0>{}, std::integral_constant<int, RP::IO>{}, RP::x3);
       if (x_post) measure_x_post(LIO{}, sc);
       apply_nibble<RP::IO, KIND, qm(RP::IO), FR>(v, R, kTileBits);
+      if constexpr (XE) {
+        if (x_end) measure_x_end(LIO{}, sc * nib_w2(RP::IO, kTileBits));
+      }
     }
     xch_f(std::integral_constant<int, RP::pIO>{}, std::integral_constant<int, RP::IO>{}, RP::x4);
     if constexpr (kRho) rho_apply(LIO{}, kTileBits, v, 0);
@@ -1394,7 +1441,22 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
     xch_f(std::integral_constant<int, RP::d_lay>{}, std::integral_constant<int, RP::IO>{}, RP::x5);
   }
   if constexpr (MC > 0) {
-    if (A.meas != kMeasNone && A.meas_at_end) measure_in(LIO{}, 1.0);
+    if constexpr (XE) {
+      // the Z part after the post-kick, in layout 2: layout 1 would hold two
+      // bonds between a register bit and a lane bit (sites 3-4 and 7-8 of a
+      // 12-site tile) where the combine carries one; the pass stores nothing
+      // (the chain's last), so the extra re-layout costs no store order.  (A
+      // kick-only pass takes it mid-pass, after its only kicks.)
+      if constexpr (RP::post) {
+        if (A.meas_at_end && (A.meas_parts & kPartZ)) {
+          using L2 = std::integral_constant<int, 2>;
+          xch_tile<SPLIT, RP::IO, 2>(v, s_tile, s_half, t);
+          measure_in(L2{}, 1.0);
+        }
+      }
+    } else {
+      if (A.meas != kMeasNone && A.meas_at_end) measure_in(LIO{}, 1.0);
+    }
   }
   DTC_TS(5);
 
@@ -1413,6 +1475,8 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
   const uint32_t sofs = (uint32_t)sofs64;
   if constexpr (NS) {
     // measurement-only pass (the last of an echo chain): nothing to write
+  } else if (XE && A.no_store) {
+    // (the same, chosen at launch: the last pass of an energy echo chain)
   } else if (ofs32) {
 #pragma unroll
     for (int r = 0; r < kRegs; ++r) {
@@ -1475,17 +1539,26 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
           if constexpr (RP::nIO) finish(LIO{}, xpost, kSlotXPost);
         }
       }
+      if constexpr (XE) {
+        // the end point's sums, in the post point's slots (never both)
+        if (x_end) {
+          if constexpr (RP::nO) finish(LO{}, xend, kSlotXPost);
+          if constexpr (RP::n0) finish(L0{}, xend, kSlotXPost);
+          if constexpr (RP::nIO) finish(LIO{}, xend, kSlotXPost);
+        }
+      }
     }
     // obs [2L, 3L): X before the post-kick, [3L, 4L): X before the pre-kick
     // (0 for sites this pass does not kick), observable 2L + xo
     auto x_combine = [&](int xo) {
       const int L = A.L_real;
-      if (xo < 0 || xo >= 2 * L) return;
+      // (XE: [2L, 3L) only, X after the last kick; the rows are 3 L wide)
+      if (xo < 0 || xo >= (XE ? L : 2 * L)) return;
       const bool pre = xo >= L;
       const int site = pre ? xo - L : xo;
       const int tb = site < c ? site : ((site >= s && site < s + kTileBits - c) ? c + site - s : -1);
       double acc = 0.0;
-      if (tb >= 0 && ((A.act >> tb) & 1) && (pre ? x_pre : x_post)) {
+      if (tb >= 0 && ((A.act >> tb) & 1) && (XE ? x_end : (pre ? x_pre : x_post))) {
         if constexpr (SPLIT && MC == 3) {
           const double* px = &s_xpart[0][pre ? 1 : 0][tb >> 2][(tb & 3) << 3];
           constexpr int kW = 2 * 3 * 32;  // doubles per wave
@@ -1499,11 +1572,11 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
       }
       A.partial[(b * n_tiles + tile) * A.n_obs + 2 * L + xo] = acc;
     };
-    if (zc_lay >= 0 || x_pre || x_post) {
+    if (zc_lay >= 0 || x_pre || x_post || x_end) {
       __syncthreads();
       if (zc_lay >= 0) site_combine(zc_lay, zc_inv, t);
       // X on wave 2 (2L <= 64), beside wave 0's Z / ZZ combine
-      if (x_pre || x_post) x_combine(t - 2 * kWaveSize);
+      if (x_pre || x_post || x_end) x_combine(t - 2 * kWaveSize);
     }
   }
 #ifdef DTC_PHASE_TIMING
@@ -1579,6 +1652,15 @@ template <int NIBS, int KIND>
 __global__ __launch_bounds__(kThreads, 2) void dtc_kick_xfinal(PassArgs A) {
   pass_body<kShapeK, NIBS, KIND, 3, true>(A);
 }
+// The ends of an energy echo chain (dtc_energy_echo): the pass that applies a
+// site group's last kick layer measures X of the group after it (kPartXEnd),
+// the chain's last pass also norm, Z, ZZ of all sites at its end and stores
+// nothing (PassArgs::no_store).  K-D-K / D-K: the last layer is the post-kick;
+// K: the trailing kick-only pass of the other groups.
+template <int SHAPE, int NIBS, int KIND>
+__global__ __launch_bounds__(kThreads, 2) void dtc_xend_pass(PassArgs A) {
+  pass_body<SHAPE, NIBS, KIND, 3, false, false, false, kGeoStd, true>(A);
+}
 template <int NIBS, int MC, int GEO = kGeoStd>
 __global__ __launch_bounds__(kThreads, 2) void dtc_diag_pass(PassArgs A) {
   pass_body<kShapeD, NIBS, kKindRX, MC, false, false, false, GEO>(A);
@@ -1587,6 +1669,24 @@ __global__ __launch_bounds__(kThreads, 2) void dtc_diag_pass(PassArgs A) {
 template <int NIBS, int KIND, int MC, int GEO = kGeoStd>
 hipError_t launch_shape(const PassArgs& a, dim3 grid, int shape, hipStream_t stream) {
   dim3 block(kThreads);
+  if constexpr (MC == 3 && GEO == kGeoStd) {
+    if (a.meas_parts & kPartXEnd) {
+      // an end of an energy echo chain, stored or (the chain's last) not
+      // (the Z part: at the end of a pass with a post-kick, mid-pass in a
+      // kick-only one; only on the chain's last pass, which stores nothing)
+      if ((a.meas_parts & (kPartXPre | kPartXPost)) || a.dst2 || a.basis ||
+          (a.meas_at_end != 0) != (shape != kShapeK) ||
+          ((a.meas_parts & kPartZ) != 0) != (a.no_store != 0) || a.n_obs != 3 * a.L_real)
+        return hipErrorInvalidValue;
+      switch (shape) {
+        case kShapeKDK: hipLaunchKernelGGL((dtc_xend_pass<kShapeKDK, NIBS, KIND>), grid, block, 0, stream, a); break;
+        case kShapeDK: hipLaunchKernelGGL((dtc_xend_pass<kShapeDK, NIBS, KIND>), grid, block, 0, stream, a); break;
+        case kShapeK: hipLaunchKernelGGL((dtc_xend_pass<kShapeK, NIBS, KIND>), grid, block, 0, stream, a); break;
+        default: return hipErrorInvalidValue;
+      }
+      return hipGetLastError();
+    }
+  }
   if (a.no_store) {
     if constexpr (MC == 3) {
       if (shape != kShapeK) return hipErrorInvalidValue;
@@ -1718,7 +1818,7 @@ hipError_t launch_pass(const PassArgs& a, int batch, int shape, int kind, hipStr
   int nibs = 0;
   for (int n = 0; n < 3; ++n)
     if (a.act & (0xF << (4 * n))) nibs |= 1 << n;
-  const bool xm = a.meas == kMeasEnergy && (a.meas_parts & (kPartXPre | kPartXPost));
+  const bool xm = a.meas == kMeasEnergy && (a.meas_parts & (kPartXPre | kPartXPost | kPartXEnd));
   const int mc = a.meas == kMeasNone ? 0 : (a.meas == kMeasProbe ? 1 : (xm ? 3 : 2));
   switch (nibs) {
     case 4: return launch_kind<4>(a, grid, shape, kind, mc, stream);

@@ -24,6 +24,12 @@ noiselessly, as Aer executes the estimator's appended basis change outside the
 noise model's u1/u2/u3 gates); any Hamiltonian variant of the scripts
 ("full", "z_only", "zz_only", "x_only", "z_zz") is a linear combination.
 
+Echo (``echo=True``; ``qc_qiskit(..., echo=True)`` of every energy script,
+energy.py:141-153: ``UF_subcircuit.inverse()`` t times after the t forward
+periods, one uncomment away in each driver): the same observables of the
+Loschmidt echo state from ``dtc_energy_echo_sums``.  Without noise it is the
+initial state's energy at every t.  Depolarizing or noiseless kicks only.
+
 Noise accumulation (energy.py:212-218): the script adds
 ``depolarizing_error(nprob)`` to ONE NoiseModel inside its loop over
 ``nprobs``, so Aer composes the errors; depolarizing channels compose to
@@ -40,7 +46,7 @@ import os
 
 import numpy as np
 
-from .engine import SweepSpec, energy_init_mask
+from .engine import SweepSpec, energy_init_mask, refuse_energy_echo
 
 HAMILTONIAN_TYPES = ("full", "z_only", "zz_only", "x_only", "z_zz")
 ESTIMATOR_SHOTS = int(math.ceil(1.0 / 0.015625 ** 2))  # BackendEstimatorV2 default precision
@@ -142,16 +148,23 @@ def energy_spec(L, T, hs, phis, g, initial_state="vacuum", **kw) -> SweepSpec:
 
 def get_instances_energy(spec: SweepSpec, n_traj: int = ESTIMATOR_SHOTS,
                          hamiltonian_types=("full",), seed: int = 0x5EED0001, engine=None,
-                         traj_offset: int = 0, readout=None) -> dict:
+                         traj_offset: int = 0, readout=None, echo: bool = False) -> dict:
     """``get_instances`` of the energy scripts: ``<H>(t)`` per instance
     (``[inst][T]``) for each requested Hamiltonian variant, as the trajectory
     mean of the engine's observables (``readout`` = per-site (p01, p10)
     applied to them, device-like noise).  <H> and the read-out map are affine
     in the observables, so the means come from the engine's on-device
     trajectory sums (``energy_sums``, dtc_energy_sums; ``energy_sums_bond``
-    when the spec carries bond noise)."""
+    when the spec carries bond noise).  ``echo=True``: the energy of the echo
+    state (``energy_echo_sums``); raises NotImplementedError for device-like
+    or bond noise."""
+    if echo:
+        refuse_energy_echo(spec, "get_instances_energy(echo=True)")
     eng = _engine(engine)
-    run = eng.energy_sums_bond if spec.has_bond_noise else eng.energy_sums
+    if echo:
+        run = eng.energy_echo_sums
+    else:
+        run = eng.energy_sums_bond if spec.has_bond_noise else eng.energy_sums
     sums = run(spec, n_traj, seed=seed, traj_offset=traj_offset)
     obs = {k: v / n_traj for k, v in sums.items()}
     if readout is not None:
@@ -178,18 +191,20 @@ def energy_folder(L: int, variant: str = "full-ham") -> str:
 
 
 def energy_csv_name(prefix, state, g, L, inst, randomphi, delta, amplitude, noise, use_noise,
-                    bond_noise_prob=0.0):
+                    bond_noise_prob=0.0, echo=False):
     """The scripts' file names; with bond noise (no reference counterpart)
-    ``_bond{p}`` before the extension, as ``sweep.autocorr_csv_name``."""
+    ``_bond{p}`` before the extension, as ``sweep.autocorr_csv_name``; the echo
+    energy's files (the scripts never saved one) ``_echo``."""
     bond = f"_bond{bond_noise_prob}" if bond_noise_prob else ""
+    tail = "_echo" if echo else ""
     return (f"{prefix}_{state}_g{g}_L{L}_inst{inst}_randomphi{randomphi}_delta{delta}"
-            f"_amplitude{amplitude}_noise{noise}_usenoise{use_noise}{bond}.csv")
+            f"_amplitude{amplitude}_noise{noise}_usenoise{use_noise}{bond}{tail}.csv")
 
 
 def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
                initial_state="vacuum", n_traj=ESTIMATOR_SHOTS, seed=0x5EED0001,
                hamiltonian_types=("full",), accumulate=True, engine=None, calibration=None,
-               bond_noise=None):
+               bond_noise=None, echo=False):
     """energy.py's main loop (:212-222): for each nprob, ``av_energy / L`` per
     Hamiltonian variant.  Returns ``{(ht, nprob): [T]}``.
 
@@ -200,7 +215,10 @@ def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
     with per-site read-out error.
 
     ``bond_noise`` (a float or an [L-1] array): ``depolarizing_error(p, 2)``
-    after every RZZ, in every column (SweepSpec.bond_noise)."""
+    after every RZZ, in every column (SweepSpec.bond_noise).
+
+    ``echo=True``: every column is the echo energy (``get_instances_energy``);
+    not with ``calibration`` or bond noise."""
     eff = accumulated_noise(nprobs) if accumulate else [float(p) for p in nprobs]
     res = {}
     for k, (nprob, p_eff) in enumerate(zip(nprobs, eff)):
@@ -215,21 +233,27 @@ def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
             readout = calibration.site_readout(L)
             run_seed = seed + 7919 * k
         per = get_instances_energy(spec, n_traj, hamiltonian_types, run_seed, engine,
-                                   readout=readout)
+                                   readout=readout, echo=echo)
         for ht, v in per.items():
             res[(ht, nprob)] = v.mean(axis=0) / L
     return res
 
 
 def run_energy_device(L, g, hs, phis, T, calibration, initial_state="vacuum",
-                      n_traj=ESTIMATOR_SHOTS, seed=0x5EED0001, engine=None, bond_noise=None):
+                      n_traj=ESTIMATOR_SHOTS, seed=0x5EED0001, engine=None, bond_noise=None,
+                      echo=False):
     """energy-fakebrisbane.py's main loop (:226-234): ``<H>(t)`` under the
     device's noise (here: device-like noise from a calibration file, see
     device_noise.py; FakeBrisbane's own data is unavailable offline), read-out
     error on every measured site, mean over instances — NOT divided by L (the
     script saves ``np.mean(energy, axis=0)`` as is).  ``calibration=None``:
     the script with ``--use_fakebackend 0`` (an empty NoiseModel: noiseless).
-    ``bond_noise``: as in ``run_energy``."""
+    ``bond_noise``: as in ``run_energy``.  ``echo=True`` runs only with
+    ``calibration=None`` (the noiseless echo) and raises otherwise."""
+    if echo and calibration is not None:
+        raise NotImplementedError(
+            "run_energy_device(echo=True) does not support device-like noise (a calibration): "
+            "the energy echo runs depolarizing or noiseless kicks only")
     spec = energy_spec(L, T, hs, phis, g, initial_state, noise_prob=0.0,
                        use_noise=1 if calibration is not None else 0, bond_noise=bond_noise)
     readout = None
@@ -238,7 +262,7 @@ def run_energy_device(L, g, hs, phis, T, calibration, initial_state="vacuum",
         readout = calibration.site_readout(L)
     noisy = calibration is not None or spec.has_bond_noise
     per = get_instances_energy(spec, n_traj if noisy else 1, ("full",), seed,
-                               engine, readout=readout)["full"]
+                               engine, readout=readout, echo=echo)["full"]
     return per.mean(axis=0)
 
 

@@ -16,6 +16,11 @@ Flags as energy.py:26-40; files and folders as the scripts write them
 (energy.py:57-61, 229-234; ham-comparison.py:277-280; vs-echo.py:248-251).
 Values are ``mean over instances of <H>(t) / L`` except for fakebrisbane.
 
+``--echo 1`` (modes full, ham-comparison, vs-echo): every column is the energy of
+the Loschmidt echo state, ``qc_qiskit(..., echo=True)`` of the scripts
+(energy.py:141-153); the file name gains ``_echo`` before ``.csv``, the folder is
+unchanged.  Not with device-like noise or bond noise.
+
 ``--use_fakebackend`` defaults as in each script (1 for vs-echo and fakebrisbane,
 0 otherwise).  With 1 the noise is device-like noise from ``--device_calibration``
 (FakeBrisbane's own snapshot ships inside qiskit-ibm-runtime and is not available
@@ -55,6 +60,9 @@ def build_parser():
                    help="1 (with --use_fakebackend 1) = the calibration's two-qubit gate error as "
                         "the bond noise (file names gain _bondcal); 0 = none")
     p.add_argument("--initial_state", type=str, default="vacuum", choices=["vacuum", "neel"])
+    p.add_argument("--echo", type=int, default=0, choices=[0, 1],
+                   help="1 = the energy of the echo state (t inverse periods after the t forward "
+                        "ones); modes full, ham-comparison, vs-echo; file names gain _echo")
     p.add_argument("--use_fakebackend", type=int, default=None,
                    help="default: 1 for --mode vs-echo / fakebrisbane, else 0 (as the scripts)")
     p.add_argument("--device_calibration", type=str, default=None,
@@ -77,6 +85,17 @@ def main(argv=None):
     use_fake = args.use_fakebackend
     if use_fake is None:
         use_fake = 1 if args.mode in ("vs-echo", "fakebrisbane") else 0
+    echo = bool(args.echo)
+    if echo:
+        # refused before anything runs; the messages are the engine's
+        if args.mode == "fakebrisbane":
+            raise SystemExit("--echo 1 is not available in --mode fakebrisbane")
+        if use_fake:
+            raise SystemExit("--echo 1: the energy echo does not support device-like noise "
+                             "(--use_fakebackend 1); pass --use_fakebackend 0")
+        if args.bond_noise_prob or args.fakebackend_bond:
+            raise SystemExit("--echo 1: the energy echo does not support bond noise "
+                             "(--bond_noise_prob / --fakebackend_bond)")
     cal = None
     if use_fake:
         from .cli import DEFAULT_CALIBRATION
@@ -88,7 +107,8 @@ def main(argv=None):
     from .cli import bond_from_args
 
     bond, bond_tag = bond_from_args(args, cal, L)
-    tagged = (lambda prefix: en.energy_csv_name(prefix, *name_args, bond_noise_prob=bond_tag))
+    tagged = (lambda prefix: en.energy_csv_name(prefix, *name_args, bond_noise_prob=bond_tag,
+                                                echo=echo))
     if args.mode == "fakebrisbane":
         e = en.run_energy_device(L, args.g, hs, phis, T, cal, initial_state=args.initial_state,
                                  n_traj=args.trajectories, seed=args.seed,
@@ -101,7 +121,7 @@ def main(argv=None):
         noisy = bool(args.use_noise)
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=int(noisy),
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal, bond_noise=bond)
+                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo)
         cols = {f"energy_p_{p}": res[("full", p)] for p in nprobs}
         path = os.path.join(args.out_dir, en.energy_folder(L, "full-ham"),
                             tagged("energy_data"))
@@ -109,7 +129,7 @@ def main(argv=None):
         nprobs = [args.noise_prob]
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=1,
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal, bond_noise=bond,
+                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo,
                             hamiltonian_types=("z_only", "zz_only", "x_only", "full"))
         cols = {}
         for p in nprobs:
@@ -124,7 +144,7 @@ def main(argv=None):
         nprobs = [0.1]
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=1,
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal, bond_noise=bond,
+                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo,
                             hamiltonian_types=("full", "z_zz"))
         cols = {}
         for p in nprobs:
@@ -167,6 +187,8 @@ def write_comprehensive(args, ts, e_with, e_without):
         name = "comprehensive_data_" + tail
     else:
         name = "comprehensive_data_energy_only_" + tail
+    if args.echo:
+        name = name[:-len(".csv")] + "_echo.csv"
     path = os.path.join(args.out_dir, en.energy_folder(L, "ham-comparison"), name)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     pd.DataFrame(data).to_csv(path, index=False)

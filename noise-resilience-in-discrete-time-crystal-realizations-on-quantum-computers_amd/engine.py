@@ -138,6 +138,19 @@ def refuse_bond_noise(spec: SweepSpec, what: str, instead: str | None = None) ->
                "only DtcEngine.autocorr, energy_bond and energy_sums_bond do"))
 
 
+def refuse_energy_echo(spec: SweepSpec, what: str) -> None:
+    """The energy echo runs depolarizing or noiseless kicks only."""
+    if getattr(spec, "device", None) is not None:
+        raise NotImplementedError(
+            f"{what} does not support device-like noise (SweepSpec.device): nothing may be "
+            "measured across a Kraus kick, so the echo chains' ends would need stored states "
+            "and X-basis passes, which are not built")
+    if getattr(spec, "has_bond_noise", False):
+        raise NotImplementedError(
+            f"{what} does not support bond noise (SweepSpec.bond_noise): its per-state "
+            "diagonal tables and plain chains are not built for the energy echo")
+
+
 def bond_struct(p_bond: np.ndarray) -> "_capi.DtcBondNoise":
     b = _capi.DtcBondNoise()
     b.p_bond = _capi.as_dptr(p_bond)
@@ -426,6 +439,38 @@ class DtcEngine:
             ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj), _capi.as_dptr(z),
             _capi.as_dptr(zz) if L > 1 else None, _capi.as_dptr(x)))
         return {"z": z, "zz": zz, "x": x}
+
+    def _energy_echo(self, fn, spec: SweepSpec, lead: tuple, n_traj: int, seed: int,
+                     traj_offset: int, batch: int, t_first: int):
+        T, L = spec.T, spec.L
+        z = np.zeros(lead + (T, L))
+        zz = np.zeros(lead + (T, max(L - 1, 0)))
+        x = np.zeros(lead + (T, L))
+        pr = self._problem(spec, False, True, batch, t_first)
+        _capi.check(fn(
+            self._ctx, ctypes.byref(pr), ctypes.byref(self._noise(spec)), ctypes.c_uint64(seed),
+            ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj), _capi.as_dptr(z),
+            _capi.as_dptr(zz) if L > 1 else None, _capi.as_dptr(x)))
+        return {"z": z, "zz": zz, "x": x}
+
+    def energy_echo(self, spec: SweepSpec, n_traj: int, seed: int = 0x5EED0001,
+                    traj_offset: int = 0, batch: int = 0, t_first: int = 0):
+        """``energy``'s observables of the Loschmidt echo (dtc_energy_echo): row t
+        is taken on the forward state after t + t_offset periods followed by as
+        many inverse periods -- the state ``autocorr`` measures its echo on, the
+        same trajectory bit for bit.  Rows before ``t_first`` stay 0.
+        Depolarizing or noiseless kicks only."""
+        refuse_energy_echo(spec, "energy_echo")
+        return self._energy_echo(self._lib.dtc_energy_echo, spec, (spec.n_inst, n_traj), n_traj,
+                                 seed, traj_offset, batch, t_first)
+
+    def energy_echo_sums(self, spec: SweepSpec, n_traj: int, seed: int = 0x5EED0001,
+                         traj_offset: int = 0, batch: int = 0, t_first: int = 0):
+        """``energy_echo`` summed over each instance's trajectories on the device
+        (dtc_energy_echo_sums); shapes of ``energy_sums``."""
+        refuse_energy_echo(spec, "energy_echo_sums")
+        return self._energy_echo(self._lib.dtc_energy_echo_sums, spec, (spec.n_inst,), n_traj,
+                                 seed, traj_offset, batch, t_first)
 
     def _energy_bond(self, fn, spec: SweepSpec, lead: tuple, n_traj: int, seed: int,
                      traj_offset: int, batch: int):
