@@ -456,7 +456,9 @@ int dtc_schedule_counts(dtc_ctx* ctx, int64_t* counts /* [4] */);
  * RX / RY kicks, depolarizing noise only, the octet layout; DESIGN.md section
  * 4).  On by default; an engine opened with DTC_NO_WAVEFRONT=1 in the
  * environment keeps the plain interior (the test switch), DTC_WAVEFRONT=2..4
- * sets the layer cap per pass (default 4).  Booked under DTC_KERNEL_LO_PASS. */
+ * sets the layer cap per pass (default 4; a plan must take fewer launches than
+ * the plain interior, except at cap 2, which cannot and runs its two-step passes
+ * at the plain count: a test switch).  Booked under DTC_KERNEL_LO_PASS. */
 int dtc_wavefront_count(dtc_ctx* ctx, int64_t* count);
 
 /* Device properties for reports. */

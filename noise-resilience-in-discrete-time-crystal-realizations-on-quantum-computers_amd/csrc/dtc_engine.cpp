@@ -785,16 +785,23 @@ constexpr int kWfSetStride = (dtc::kWfSteps + 1) * 2 * dtc::kWfTab;  // double2 
 dtc::PassKick wf_pass_kick(const Launch& l, int j) {
   const WfGeo& g = kWfGeo[l.wf_tile];
   dtc::PassKick pk{};
-  for (int h = 0; h < 2; ++h) {
-    const int st = 2 * j + h;
+  // (every step's layer in lc[], and the launch's program: the Pauli frame of
+  // the launch runs across both rows, dtc_wf_frame.h)
+  for (int st = 0; st < dtc::kWfSteps; ++st) {
     KickDesc k = no_kick();
     if (st < l.wf_steps && l.wf_mask[st]) {
       k = l.wf_kick[st];
       k.enabled = 1;
       k.skip = (uint32_t)g.act & ~l.wf_mask[st];
     }
-    (h ? pk.post : pk.pre) = k;
+    pk.lc[st] = k;
+    pk.wf_mask[st] = st < l.wf_steps ? l.wf_mask[st] : 0u;
   }
+  pk.pre = pk.lc[2 * j];
+  pk.post = pk.lc[2 * j + 1];
+  pk.wf_row = 1 + j;
+  pk.wf_steps = l.wf_steps;
+  pk.wf_dmask = l.wf_dmask;
   pk.kind = l.wf_kind;
   // (tile bit k < 12 = site k for the low tile: c = 12 serves the records too)
   pk.c = g.c;
@@ -1940,7 +1947,13 @@ bool wf_replace(dtc_ctx* ctx, const RunCfg& rc, std::vector<Launch>& sched, size
   p.tiles = {dtc::wf::make_tile(0, 0, 12), dtc::wf::make_tile(3, 11, 9)};
   p.cap = ctx->wf_cap;
   std::vector<dtc::wf::Pass> plan;
-  if (!dtc::wf::plan(p, plan) || (int)plan.size() >= n) return false;
+  // a plan must save launches -- except at cap 2 (DTC_WAVEFRONT=2), which lifts
+  // a tile's sites by two layers per pass, the plain rate, and never can: that
+  // setting only ever is the test switch for the two-step passes, so there a
+  // plan of the plain length runs
+  if (!dtc::wf::plan(p, plan) || (int)plan.size() > n ||
+      ((int)plan.size() == n && ctx->wf_cap != 2))
+    return false;
   std::vector<Launch> out;
   for (const dtc::wf::Pass& ps : plan) {
     Launch l = sched[r0];

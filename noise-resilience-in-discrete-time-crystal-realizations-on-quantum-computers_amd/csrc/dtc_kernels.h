@@ -214,6 +214,12 @@ struct PassKick {
   int lc_wide;          // the 10-site form: lc_mask bit 10 l + k - 2 = tile bit k of
   int8_t lc_gb[kTileBits];  // layer l, tile bit k = global bit lc_gb[k] (kLcw* records)
   uint64_t lc_mask2;    // lc_wide = 2: bits 64..83 of the 12-site form's mask
+  // a record row of a wavefront launch (wf_row = 1 + row; 0: none), for the
+  // launch's Pauli frame (dtc_wf_frame.h), which runs across both rows: the
+  // launch's step count, kicked tile bits per step and diagonals (WfArgs), and
+  // in lc[st] the layer of step st as pre / post hold it (lc_layers stays 0)
+  int wf_row, wf_steps, wf_dmask;
+  uint32_t wf_mask[4];
 };
 
 struct PrepArgs {
@@ -358,6 +364,15 @@ static constexpr int kWfSteps = 4;
 static constexpr int kWfTabA = 128;
 static constexpr int kWfTabB = 64;
 static constexpr int kWfTab = kWfTabA + kWfTabB;
+static_assert(kWfSteps == sizeof(PassKick::wf_mask) / sizeof(uint32_t) && kWfSteps <= kLcMaxLayers,
+              "PassKick holds a wavefront launch's steps");
+// Pauli-frame records (dtc_wf_frame.h; prep_kernel): every kick record holds
+// the frame-signed form-B coefficient in d[kFrameCoef]; the second block's
+// total record holds, as integers, the frame's X at the diagonal of step st in
+// bits 12 st .. 12 st + 11 of i[kWfMaskXD], and in i[kWfMaskZX] the Z mask of
+// the last diagonal applied (bits 0..11) and the X at the store (16..27).  The
+// frame's power of i is in that block's global factor.
+enum : int { kWfMaskXD = 3, kWfMaskZX = 4 };
 struct WfArgs {
   const double2* src;
   double2* dst;            // may alias src

@@ -30,6 +30,9 @@
 #include "dtc_device.h"
 #include "dtc_kernels.h"
 #include "dtc_rng.h"
+#include "dtc_wf_frame.h"
+static_assert(dtc::kWfFrameSteps == dtc::kWfSteps && dtc::kWfFrameBits == dtc::kTileBits,
+              "dtc_wf_frame.h walks the wavefront pass's steps and tile");
 
 // Nontemporal tile loads / stores (bit 0 load, bit 1 store), per pass family:
 // A = passes over a full 12-site group (NIBS 7), B = the others.  The tile is
@@ -416,6 +419,48 @@ __device__ void frame12_records(const PassKick& pk, KickRec* out, const int* fva
   tot.i[kT12MaskZ] = md | ((ph & 3) << kT12PhShift);
 }
 
+// The Pauli-frame records of a wavefront launch's row (dtc_wf_frame.h; the
+// wavefront pass of dtc_wavefront.hip).  The frame runs across both rows of
+// the launch, so each row's thread rebuilds the other row's kicks for their
+// variants (24 more site kicks per thread) and walks all of the launch's
+// steps; it writes its own row's coefficients (d[kFrameCoef]), and the second
+// row's the masks (kWfMask*).  Returns the power of i for the row's global
+// factor.
+__device__ int wf_frame_records(const PrepArgs& P, const PassKick& pk, uint64_t traj, KickRec* out,
+                                const int* fvar, KickRec& tot) {
+  constexpr int NT = kTileBits;
+  const int row = pk.wf_row - 1;
+  int var[kWfSteps][NT];
+  double coef[kWfSteps][NT];
+  for (int st = 0; st < kWfSteps; ++st) {
+    const KickDesc& K = pk.lc[st];
+    for (int k = 0; k < NT; ++k) {
+      if ((st >> 1) == row) {
+        var[st][k] = fvar[(st & 1) * NT + k];
+        coef[st][k] = out[(st & 1) * NT + k].d[0];
+        continue;
+      }
+      const int lsite = k < pk.c ? k : pk.s + k - pk.c;
+      double2 m[4] = {make_double2(1.0, 0.0), make_double2(0.0, 0.0), make_double2(0.0, 0.0),
+                      make_double2(1.0, 0.0)};
+      if (K.enabled && (pk.act & ~(int)K.skip & (1 << k)) && lsite < P.L_real)
+        build_site_kick(P, K, P.site_of ? P.site_of[lsite] : lsite, traj, m);
+      SiteMat sm;
+      canonicalise(pk.kind, m, sm);
+      var[st][k] = sm.var;
+      coef[st][k] = sm.coef;
+    }
+  }
+  WfFrame fr;
+  wf_frame_walk(pk.kind == kKindRX, pk.wf_steps, pk.wf_mask, pk.wf_dmask, pk.act, var, coef, fr);
+  for (int h = 0; h < 2; ++h)
+    for (int k = 0; k < NT; ++k) out[h * NT + k].d[kFrameCoef] = fr.coef[2 * row + h][k];
+  if (row != 1) return 0;
+  tot.i[kWfMaskXD] = (long long)fr.xdiag;
+  tot.i[kWfMaskZX] = fr.zlast | (fr.xend << 16);
+  return fr.ph;
+}
+
 // Kick records (dtc_kernels.h: KickRec) of n_pass passes x batch states: one
 // thread per (pass, state) builds the 24 noisy site kicks of the pass, writes
 // their factored forms and the product of their global factors.
@@ -548,7 +593,8 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs P) {
   // (the 12-bit passes' frame records, pass_body FR: nibble sets 6 and 7 of
   // the standard geometry -- not the 13 / 7 split's 7-site column group)
   const bool frame12 = tb == kTileBits && (pk.kind == kKindRX || pk.kind == kKindRY) &&
-                       (pk.act & 0xF0) && (pk.act & 0xF00) && !(pk.c == kB7Cols && pk.act == 0xFE0);
+                       (pk.act & 0xF0) && (pk.act & 0xF00) && !(pk.c == kB7Cols && pk.act == 0xFE0) &&
+                       !pk.wf_row;
   int fvar[2 * kMaxTileBits];
   for (int half = 0; half < 2; ++half) {
     const KickDesc& K = half == 0 ? pk.pre : pk.post;
@@ -583,7 +629,7 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs P) {
         for (int e = 3; e < 8; ++e) r.d[e] = 0.0;
       }
       out[half * tb + k] = r;
-      if (frame13 || frame12) fvar[half * tb + k] = sm.var;
+      if (frame13 || frame12 || pk.wf_row) fvar[half * tb + k] = sm.var;
       ksum += sm.k;
       w[half] *= sm.scale;
     }
@@ -592,6 +638,8 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs P) {
   for (int e = 0; e < 8; ++e) tot.d[e] = 0.0;
   if (frame13) ksum += frame13_records(pk, out, fvar, tot);
   if (frame12) frame12_records(pk, out, fvar, tot);
+  if (pk.wf_row && tb == kTileBits && (pk.kind == kKindRX || pk.kind == kKindRY))
+    ksum += wf_frame_records(P, pk, traj, out, fvar, tot);
   const int kph = ksum & 3;
   const double wg = w[0] * w[1];
   tot.d[0] = kph == 0 ? wg : (kph == 2 ? -wg : 0.0);

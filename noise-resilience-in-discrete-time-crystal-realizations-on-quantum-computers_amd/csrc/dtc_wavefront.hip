@@ -5,10 +5,12 @@
 // 0..2 as 128-B columns + sites 11..19; the shared site 11 lets each pass lift
 // its own sites by several layers.
 //
-// Kicks: the factored RX / RY butterflies of the plain passes in their variant
-// form, from two consecutive standard record blocks per state (steps 0, 1 =
-// the first block's pre / post layer, steps 2, 3 the second's; skipped tile
-// bits carry identity records).  Diagonals: per (instance, step) a 128-entry
+// Kicks: the factored RX / RY butterflies of the plain passes in Pauli-frame
+// form (dtc_wf_frame.h: one form-B butterfly per kick, no variant branch; the
+// frame's X rides to the store, its Z to the last diagonal), from two
+// consecutive standard record blocks per state (steps 0, 1 = the first
+// block's pre / post layer, steps 2, 3 the second's; skipped tile bits carry
+// identity records).  Diagonals: per (instance, step) a 128-entry
 // table over tile bits 0..6 (their fields, the bonds among them) and a 64-entry
 // table over bits 6..11, staged for the workgroup's value of the one index bit
 // outside the tile that a bond reaches (a sign on the in-tile site's angle).
@@ -95,16 +97,36 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
       v[r] = make_double2(w.x, w.y);
     }
   }
+  // The Pauli frame of the launch (dtc_wf_frame.h; masks in the second block's
+  // total record): the table of step st is staged X-permuted by the frame's X
+  // at that diagonal -- entry i goes to i ^ x, each table with its part of the
+  // mask -- and the last diagonal's takes the Z flush as a sign per entry (a
+  // parity of the staged index; tile bit 6 counts in the 6..11 table).  Done at
+  // the LDS write, so the scalar loads of the masks wait behind the tile's
+  // loads, not in front of them.
+  const RecScalar R0(A.recs + b * kRecPerState);
+  const RecScalar R1(A.recs + ((int64_t)A.batch + b) * kRecPerState);
+  const long long fxd = R1.bits(8 * kRecTotal + kWfMaskXD);
+  const int fzx = R1.i(kRecTotal, kWfMaskZX);
   if (t < kWfTab) {
+    const int last = 31 - __builtin_clz(A.dmask | 1);
+    const int fz = fzx & (kTile - 1);
+    const bool hi = t >= kWfTabA;
+    const int ti = hi ? t - kWfTabA : t;
+    const int zt = hi ? fz >> 6 : fz & 63;
 #pragma unroll
-    for (int st = 0; st <= kWfSteps; ++st) s_tab[st * kWfTab + t] = stage[st];
+    for (int st = 0; st <= kWfSteps; ++st) {
+      const int fx = (int)(fxd >> (kTileBits * st)) & (kTile - 1);
+      const int j = ti ^ (hi ? fx >> 6 : fx & (kWfTabA - 1));
+      const bool neg = st == last && (__popc(j & zt) & 1);
+      s_tab[st * kWfTab + (hi ? kWfTabA : 0) + j] =
+          neg ? make_double2(-stage[st].x, -stage[st].y) : stage[st];
+    }
   }
   __syncthreads();
 
-  // the kicks' global factor (both record blocks'), folded into the first
-  // diagonal applied
-  const RecScalar R0(A.recs + b * kRecPerState);
-  const RecScalar R1(A.recs + ((int64_t)A.batch + b) * kRecPerState);
+  // the kicks' global factor (both record blocks', the frame's power of i in
+  // the second), folded into the first diagonal applied
   double2 gf = cmul(make_double2(R0.d(kRecTotal, 0), R0.d(kRecTotal, 1)),
                     make_double2(R1.d(kRecTotal, 0), R1.d(kRecTotal, 1)));
   auto diag = [&](auto lay, int st) {
@@ -116,7 +138,7 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
     constexpr int N = decltype(nib)::value;
     if (!(A.mask[st] & (0xFu << (4 * N)))) return;
     const RecScalar R(A.recs + ((int64_t)(st >> 1) * A.batch + b) * kRecPerState);
-    apply_nibble<N, KIND, N == 0 ? QM0 : 15>(v, R, (st & 1) * kTileBits);
+    apply_nibble<N, KIND, N == 0 ? QM0 : 15, /*FRAME=*/true>(v, R, (st & 1) * kTileBits);
   };
   using L0 = std::integral_constant<int, 0>;
   using L1 = std::integral_constant<int, 1>;
@@ -149,18 +171,31 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
   } else {
     diag(L2{}, n);
   }
-  if (gf.x != 1.0 || gf.y != 0.0) {
+  // a launch without any diagonal: the global factor and the frame's Z here
+  // (layout 2: the thread's bits 0..7, the registers' 8..11)
+  if (!A.dmask) {
+    const int fz = fzx & (kTile - 1);
+    const double sg = (__popc(t & fz) & 1) ? -1.0 : 1.0;
 #pragma unroll
-    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], gf);
+    for (int r = 0; r < kRegs; ++r) {
+      const double s = (__popc(r & (fz >> 8)) & 1) ? -sg : sg;
+      v[r] = cmul(v[r], make_double2(s * gf.x, s * gf.y));
+    }
   }
+  // The frame's X leaves at the store: tile index y goes to y ^ x.  The thread
+  // bits' part moves the lane's base; the register bits' part (tile bits
+  // 8..11, uniform) picks each register's row, sixteen scalar offsets.  No
+  // work per amplitude.
   {
-    double2* dst = A.dst + sbase + vofs;
+    const int fx = (fzx >> 16) & (kTile - 1);
+    const int xr = fx >> 8;
+    double2* dst = A.dst + sbase + octet_spread(M.at(ybase<2>(t) ^ (fx & 255)), og);
 #pragma unroll
     for (int r = 0; r < kRegs; ++r) {
       d2v x;
       x.x = v[r].x;
       x.y = v[r].y;
-      __builtin_nontemporal_store(x, (d2v*)(dst + octet_spread(M.rel(r << 8), og)));
+      __builtin_nontemporal_store(x, (d2v*)(dst + octet_spread(M.rel((r ^ xr) << 8), og)));
     }
   }
 }
@@ -176,6 +211,8 @@ hipError_t launch_wavefront(const WfArgs& a, int kind, hipStream_t stream) {
   if (!cols3 && a.c != kTileBits) return hipErrorInvalidValue;
   for (int st = 0; st < a.n_steps; ++st)
     if (a.mask[st] >> kTileBits || (cols3 && (a.mask[st] & 7u))) return hipErrorInvalidValue;
+  // (the frame's Z leaves by the last diagonal: none beyond the trailing one)
+  if (a.dmask < 0 || a.dmask >> (a.n_steps + 1)) return hipErrorInvalidValue;
   const int n_tiles = 1 << (a.L_eff - kTileBits);
   const dim3 grid = a.octet_bits ? dim3(n_tiles * 8, (a.batch + 7) / 8) : dim3(n_tiles, a.batch);
   const dim3 block(kThreads);

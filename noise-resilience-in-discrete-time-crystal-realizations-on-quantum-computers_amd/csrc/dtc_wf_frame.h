@@ -1,0 +1,111 @@
+// dtc_wf_frame.h -- the Pauli frame of one wavefront launch (dtc_wavefront.hip),
+// host and device: the prep kernel runs it per state (dtc_kernels.hip), and
+// tools/wavefront_frame_check.cpp runs the same code on the CPU against the
+// direct 2x2 products.
+//
+// The pass runs one butterfly for every kick, the form-B one G(f) (RX: f I +
+// i X; RY: f I + i Y), as frame12_records / frame13_records do for the plain
+// passes: form A is A(beta) = -i X G(-beta) (RX) or X Z G(-beta) (RY),
+// sigma = -1 a Z after the kick.  The true tile is i^ph X^x Z^z (the computed
+// tile); a kick Z^n X^a G(g) on tile bit k runs as G(+-g) (G past the frame:
+// RX flips g with Z_k, RY with X_k xor Z_k) and the frame takes Z^n X^a.
+// Unlike the plain passes nothing is flushed on the way: X stays in the frame
+// to the store, and a partial diagonal under the frame X^x is the same table
+// read at index y ^ x -- the kernel stages its per-workgroup tables with that
+// XOR.  Z commutes with the diagonals; it leaves as a sign on the last
+// diagonal's staged entries, together with the Z of the kicks that follow that
+// diagonal pulled back through them (frame12_records' npost; their bits depend
+// on the variants only), so the frame is X^x alone at the store, which writes
+// tile index y to y ^ x.  (A launch without any diagonal signs the tile where
+// it applies the global factor.)
+//
+// Steps as the kernel runs them: a diagonal before step st where dmask has bit
+// st (bit n_steps: the trailing one), then the butterflies of every nibble
+// that mask[st] touches, on all of the nibble's site bits (`act`: a site that
+// mask[st] leaves out carries the identity record, variant 0 with coefficient
+// 0, which is G(0) with an X for the frame like any form A).  The order of the
+// nibbles within a step does not matter here: a step kicks a site once and the
+// frame is a product over sites.
+#pragma once
+#include <stdint.h>
+
+// (no other header: the CPU check compiles this file with a plain host
+// compiler; dtc_kernels.hip asserts that the two constants are WfArgs')
+#ifdef __HIPCC__
+#define DTC_WF_HD __host__ __device__
+#else
+#define DTC_WF_HD
+#endif
+
+namespace dtc {
+
+static constexpr int kWfFrameSteps = 4;   // kWfSteps
+static constexpr int kWfFrameBits = 12;   // kTileBits
+
+struct WfFrame {
+  double coef[kWfFrameSteps][kWfFrameBits];  // the signed G coefficient of (step, tile bit)
+  uint64_t xdiag;  // bits 12 st .. 12 st + 11: the frame's X at the diagonal of step st
+  int zlast;       // the Z mask folded into the last diagonal applied (none: at the end)
+  int xend;        // the frame's X at the store
+  int ph;          // the frame's extra power of i
+};
+
+// the tile bits whose butterflies run in a step that kicks `mask`
+DTC_WF_HD inline int wf_step_bits(uint32_t mask, int act) {
+  int m = 0;
+  for (int n = 0; n < 3; ++n)
+    if (mask & (0xFu << (4 * n))) m |= 0xF << (4 * n);
+  return m & act;
+}
+
+// var, coef: the standard records' variant (SiteMat::var) and coefficient of
+// (step, tile bit)
+DTC_WF_HD inline void wf_frame_walk(bool rx, int n_steps, const uint32_t* mask, int dmask,
+                                    int act, const int (*var)[kWfFrameBits],
+                                    const double (*coef)[kWfFrameBits], WfFrame& o) {
+  auto form_a = [&](int st, int k) { return (var[st][k] >> 1) ^ 1; };
+  auto zbit = [&](int st, int k) {
+    return rx ? (var[st][k] & 1) : ((var[st][k] & 1) ^ form_a(st, k));
+  };
+  // where Z leaves: the last diagonal applied, or the end of a launch without
+  // any (the kernel then signs the tile with its global factor)
+  int last = n_steps;
+  for (int st = 0; st < n_steps; ++st)
+    if ((dmask >> st) & 1) last = st;
+  if ((dmask >> n_steps) & 1) last = n_steps;
+  int npost = 0;
+  for (int st = last; st < n_steps; ++st) {
+    const int bits = wf_step_bits(mask[st], act);
+    for (int k = 0; k < kWfFrameBits; ++k)
+      if ((bits >> k) & 1) npost ^= zbit(st, k) << k;
+  }
+  int x = 0, z = 0, ph = 0;
+  o.xdiag = 0;
+  o.zlast = 0;
+  for (int st = 0; st <= n_steps; ++st) {
+    if ((dmask >> st) & 1) o.xdiag |= (uint64_t)x << (kWfFrameBits * st);
+    if (st == last) {
+      o.zlast = z ^ npost;
+      z = npost;
+    }
+    for (int k = 0; k < kWfFrameBits; ++k) {
+      if (st < kWfFrameSteps) o.coef[st][k] = 0.0;
+      if (st == n_steps || !((wf_step_bits(mask[st], act) >> k) & 1)) continue;
+      const int fa = form_a(st, k), n2 = zbit(st, k);
+      const double g = fa ? -coef[st][k] : coef[st][k];
+      const int flip = ((rx ? z : (x ^ z)) >> k) & 1;
+      o.coef[st][k] = flip ? -g : g;
+      ph += (rx ? 3 * fa : 2 * fa) + 2 * flip;
+      x ^= fa << k;
+      ph += 2 * (n2 & (x >> k) & 1);
+      z ^= n2 << k;
+    }
+  }
+  for (int st = n_steps + 1; st < kWfFrameSteps; ++st)
+    for (int k = 0; k < kWfFrameBits; ++k) o.coef[st][k] = 0.0;
+  o.xend = x;
+  o.ph = ph & 3;
+}
+
+}  // namespace dtc
+#undef DTC_WF_HD
