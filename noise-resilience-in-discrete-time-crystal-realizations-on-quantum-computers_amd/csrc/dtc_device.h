@@ -212,16 +212,65 @@ __device__ __forceinline__ void apply_nibble(double2 (&v)[kRegs], const Rec& R, 
 // compile-time immediates.  A thread then no longer writes only slots it read
 // itself in the previous re-layout when xw or that one's xr is nonzero: the
 // caller passes sync for those.
-template <int FROM, int TO>
+//
+// WAVE (the pair 1 -> 0, 0 -> 1 only): the re-layout without a workgroup
+// barrier.  Tile bits 10 and 11 are the wave index t >> 6 in layout 1
+// (ybase<1> puts t >> 4 at bits 8..11) and in layout 0 (t << 4), and every slot
+// function here (lds_slot, slot_add in both its forms) keeps bits 10, 11 of
+// the index apart from the rest: the 1024-slot region with those bits = w is
+// written and read by wave w alone in both layouts, so the exchange moves data
+// among the lanes and registers of one wave.  A wave's LDS operations execute
+// in program order, so all its ordering points need is that the compiler keeps
+// the order: xch_order<true>, a wavefront-scope release / acquire fence pair
+// around a wave barrier, no s_barrier and no wait.  Why no other wave
+// interferes:
+//  - a wave-local exchange touches only the wave's own region, whatever the
+//    other waves are doing;
+//  - another wave touches the region only on the layout-2 side of a cross-wave
+//    exchange (2 <-> 1, 0 -> 2: these keep their barriers).  Its 2 -> 1 writes
+//    go to slots that thread read itself at the end of the last exchange into
+//    layout 2 (the rule above: nobody else uses them until the barrier behind
+//    the writes), and the last of them (the imaginary parts, in the split
+//    form) lie ahead of a barrier that this wave passes before its own final
+//    reads, so before its local exchange starts;
+//  - its X -> 2 reads come behind that exchange's first barrier, which this
+//    wave reaches only after its local exchanges and its own X -> 2 writes
+//    (layout-1 or layout-0 slots: own region) are done; the later barriers of
+//    the same exchange order the buffer's reuse as before;
+//  - the split form's reuse of the buffer for the real, then the imaginary
+//    parts of a local exchange stays inside the region: the imaginary writes
+//    follow the same wave's real reads in program order.  A 0 -> 2 that ends a
+//    pass with an odd step count is a barrier exchange like 1 -> 2.
+// The frame's X flushes on tile bits 10, 11 (xw, xr) cross waves: with such a
+// mask, or with sync, the exchange runs in the barrier form.
+static constexpr int kWaveBits = 3 << 10;  // tile bits 10, 11 = t >> 6
+template <bool WAVE>
+__device__ __forceinline__ void xch_order(bool local) {
+  if constexpr (WAVE) {
+    if (local) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      return;
+    }
+  }
+  __syncthreads();
+}
+
+template <int FROM, int TO, bool WAVE = false>
 __device__ __forceinline__ void exchange(double2 (&v)[kRegs], double2* s_tile, int t, int xw = 0,
                                          int xr = 0, bool sync = false) {
   if (FROM == TO) return;
+  static_assert(!WAVE || ((FROM == 0 || FROM == 1) && (TO == 0 || TO == 1)),
+                "wave-local re-layouts: layouts 0 and 1 only");
+  static_assert(kThreads == 256 && kTileBits == 12, "wave index = tile bits 10, 11");
   constexpr int kThrF = (kTile - 1) & ~(15 << (4 * FROM)), kThrT = (kTile - 1) & ~(15 << (4 * TO));
   const int yw = ybase<FROM>(t) ^ (xw & kThrF), yr = ybase<TO>(t) ^ (xr & kThrT);
+  const bool local = WAVE && !sync && !((xw | xr) & kWaveBits);
   if (sync) __syncthreads();
 #pragma unroll
   for (int r = 0; r < kRegs; ++r) s_tile[lds_slot(yw | (r << (4 * FROM)))] = v[r];
-  __syncthreads();
+  xch_order<WAVE>(local);
 #pragma unroll
   for (int r = 0; r < kRegs; ++r) v[r] = s_tile[lds_slot(yr | (r << (4 * TO)))];
 }
@@ -249,10 +298,16 @@ static constexpr int kHalfSlots = kTile;
 __host__ __device__ constexpr int slot_add(int y) { return y ^ ((y >> 4) & 15) ^ (((y >> 8) & 1) << 4); }
 #define DTC_SLOT(base, LAY, r) ((base) ^ slot_add((r) << (4 * (LAY))))
 #endif
-template <int FROM, int TO>
+// WAVE: the wave-local form of the 1 <-> 0 pair (exchange above), all three
+// ordering points; xw, xr are the cumulative masks here, so the write slots
+// are still the ones the thread read itself last.
+template <int FROM, int TO, bool WAVE = false>
 __device__ __forceinline__ void exchange_split(double2 (&v)[kRegs], double* s_half, int t, int xw = 0,
                                                int xr = 0) {
   if (FROM == TO) return;
+  static_assert(!WAVE || ((FROM == 0 || FROM == 1) && (TO == 0 || TO == 1)),
+                "wave-local re-layouts: layouts 0 and 1 only");
+  const bool local = WAVE && !((xw | xr) & kWaveBits);
   // the two per-thread bases are made opaque here, so every exchange forms
   // them afresh instead of the compiler keeping addresses live across the
   // kernel (the 12-site K-D-K at three workgroups per CU once spilled 80 B/lane
@@ -265,13 +320,13 @@ __device__ __forceinline__ void exchange_split(double2 (&v)[kRegs], double* s_ha
   asm volatile("" : "+v"(bf), "+v"(bt));
 #pragma unroll
   for (int r = 0; r < kRegs; ++r) s_half[DTC_SLOT(bf, FROM, r)] = v[r].x;
-  __syncthreads();
+  xch_order<WAVE>(local);
 #pragma unroll
   for (int r = 0; r < kRegs; ++r) v[r].x = s_half[DTC_SLOT(bt, TO, r)];
-  __syncthreads();
+  xch_order<WAVE>(local);
 #pragma unroll
   for (int r = 0; r < kRegs; ++r) s_half[DTC_SLOT(bf, FROM, r)] = v[r].y;
-  __syncthreads();
+  xch_order<WAVE>(local);
 #pragma unroll
   for (int r = 0; r < kRegs; ++r) v[r].y = s_half[DTC_SLOT(bt, TO, r)];
 }
@@ -321,12 +376,13 @@ __device__ __forceinline__ void exchange_split2(double2 (&v)[kRegs], double2 (&w
 
 // (Pauli-frame masks: xw, xr, sync as exchange takes them; cw, cr the
 // cumulative ones exchange_split takes)
-template <bool SPLIT, int FROM, int TO>
+// WAVE: the wave-local form of the 1 <-> 0 pair (exchange above)
+template <bool SPLIT, int FROM, int TO, bool WAVE = false>
 __device__ __forceinline__ void xch_tile(double2 (&v)[kRegs], double2* s_tile, double* s_half,
                                          int t, int xw = 0, int xr = 0, int cw = 0, int cr = 0,
                                          bool sync = false) {
-  if constexpr (SPLIT) exchange_split<FROM, TO>(v, s_half, t, cw, cr);
-  else exchange<FROM, TO>(v, s_tile, t, xw, xr, sync);
+  if constexpr (SPLIT) exchange_split<FROM, TO, WAVE>(v, s_half, t, cw, cr);
+  else exchange<FROM, TO, WAVE>(v, s_tile, t, xw, xr, sync);
 }
 
 __device__ __forceinline__ double2 diag_phase(const double2* s_chunk, int n_chunks, int64_t x) {

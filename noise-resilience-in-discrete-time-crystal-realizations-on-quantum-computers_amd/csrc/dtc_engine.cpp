@@ -31,6 +31,7 @@
 #include "dtc_kernels.h"
 #include "dtc_rng.h"
 #include "dtc_wavefront.h"
+#include "dtc_wf_frame.h"
 
 namespace {
 
@@ -1878,6 +1879,37 @@ int wf_table_set(const dtc_problem* pr, const dtc::wf::Pass& ps, bool conj, WfTa
       for (int var = 0; var < 2; ++var) {
         double* o = base + (((size_t)in * (dtc::kWfSteps + 1) + slot) * 2 + var) * dtc::kWfTab * 2;
         const double zout = var ? -1.0 : 1.0;
+        if (dtc::kWfT2Lay1 && g.c == 3 && (slot & 1)) {
+          // the column tile's odd slots: its diagonal runs in layout 1, the same
+          // factors regrouped into the register table (half 0, over tile bits
+          // 3..8) and the thread table (half 1, bits 3, 8..11), dtc_wf_frame.h
+          for (int half = 0; half < 2; ++half) {
+            const int n_ent = half ? dtc::kWfL1Thr : dtc::kWfL1Reg;
+            for (int v = 0; v < n_ent; ++v) {
+              auto z = [&](int k) {
+                const int pos = half ? dtc::wf_l1_thr_pos(k) : dtc::wf_l1_reg_pos(k);
+                return (pos >= 0 && ((v >> pos) & 1)) ? -1.0 : 1.0;
+              };
+              double ang = 0.0;
+              for (const dtc::wf::Factor& f : sp.factors) {
+                if (!f.bond) {
+                  const int k = tile_bit(f.site);
+                  if (dtc::wf_l1_in_reg(k, -1) == (half == 0)) ang += hh[f.site] * z(k);
+                } else if (in_tile(f.site) && in_tile(f.site + 1)) {
+                  const int k = tile_bit(f.site);
+                  if (dtc::wf_l1_in_reg(k, k + 1) == (half == 0)) ang += pp[f.site] * z(k) * z(k + 1);
+                } else {
+                  const int k = tile_bit(in_tile(f.site) ? f.site : f.site + 1);
+                  if (dtc::wf_l1_in_reg(k, -1) == (half == 0)) ang += pp[f.site] * z(k) * zout;
+                }
+              }
+              double* e = o + ((size_t)(half ? dtc::kWfL1Reg : 0) + v) * 2;
+              e[0] = std::cos(sgn * ang);
+              e[1] = std::sin(sgn * ang);
+            }
+          }
+          continue;
+        }
         for (int half = 0; half < 2; ++half) {
           // half 0: index = tile bits 0..6; half 1: tile bits 6..11
           const int bit0 = half ? 6 : 0, n_ent = half ? dtc::kWfTabB : dtc::kWfTabA;

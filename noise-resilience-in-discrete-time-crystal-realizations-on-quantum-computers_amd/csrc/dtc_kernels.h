@@ -364,6 +364,15 @@ static constexpr int kWfSteps = 4;
 static constexpr int kWfTabA = 128;
 static constexpr int kWfTabB = 64;
 static constexpr int kWfTab = kWfTabA + kWfTabB;
+// The column tile (c = 3; its nibble 0 holds the one site 11) snakes between
+// layouts 2 and 1 only, site 11 kicked across lanes: the tables of its odd
+// slots (1, 3) are the layout-1 pair of dtc_wf_frame.h, a register table at
+// [0, 64) and a thread table at [64, 96) of the slot.  Kernel and host table
+// builder both go by this constant (0: the three-layout snake, development A/B).
+#ifndef DTC_WF_T2_LAY1
+#define DTC_WF_T2_LAY1 1
+#endif
+static constexpr bool kWfT2Lay1 = DTC_WF_T2_LAY1 != 0;
 static_assert(kWfSteps == sizeof(PassKick::wf_mask) / sizeof(uint32_t) && kWfSteps <= kLcMaxLayers,
               "PassKick holds a wavefront launch's steps");
 // Pauli-frame records (dtc_wf_frame.h; prep_kernel): every kick record holds

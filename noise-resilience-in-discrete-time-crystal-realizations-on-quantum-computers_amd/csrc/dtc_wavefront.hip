@@ -16,7 +16,12 @@
 // outside the tile that a bond reaches (a sign on the in-tile site's angle).
 // Program: the tile snakes through the register layouts, 2 -> 1 -> 0 in even
 // steps and 0 -> 1 -> 2 in odd ones, so every step costs two LDS re-layouts and
-// the diagonals are applied in layouts 2 and 0 only.  The re-layouts go through
+// the diagonals are applied in layouts 2 and 0 only.  T2's nibble 0 holds the
+// one site 11, and tile bit 3 is lane bit 3 in layouts 1 and 2: T2 snakes
+// 2 -> 1 and 1 -> 2 only, one re-layout per step,
+// kicks site 11 across lanes (wf_kick_lane3) and applies its odd steps'
+// diagonals in layout 1 from a register / thread table pair (dtc_wf_frame.h;
+// profiles/r9_wavefront_chain_ab20.txt).  The re-layouts go through
 // a half-tile buffer (exchange_split), so three workgroups share a CU: 8.9 ms
 // per four-layer pass against 10.4 ms with the full tile at two per CU
 // (profiles/r7_wavefront_ab20.txt).
@@ -24,22 +29,37 @@
 
 #include "dtc_device.h"
 #include "dtc_kernels.h"
+#include "dtc_wf_frame.h"
 
 // Three workgroups per CU (half-tile re-layouts) or two (full-tile)
 #ifndef DTC_WF_SPLIT
 #define DTC_WF_SPLIT 1
+#endif
+// The 1 <-> 0 re-layouts of tile 1 wave-local, without workgroup barriers
+// (dtc_device.h exchange, WAVE): development A/B, off in the product -- 12 of a
+// pass's 24 barriers gone bought 0.10 ms per launch and C2 +0.5 %, under the
+// adoption bar (profiles/r9_wavefront_chain_ab20.txt)
+#ifndef DTC_WF_WAVE_XCH
+#define DTC_WF_WAVE_XCH 0
 #endif
 
 namespace dtc {
 
 // v[r] *= fac * TA[..] * TB[..] in layout LAY (2: registers = tile bits 8..11,
 // the 0..6 table is the thread's constant; 0: registers = bits 0..3, the 6..11
-// table is)
+// table is; 1, the column tile's odd steps: registers = bits 4..7, the slot
+// holds the register / thread table pair of dtc_wf_frame.h)
 template <int LAY>
 __device__ __forceinline__ void wf_diag(double2 (&v)[kRegs], const double2* tab, int t,
                                         double2 fac) {
-  static_assert(LAY == 0 || LAY == 2, "diagonals in the snake's end layouts");
-  if (LAY == 2) {
+  static_assert(LAY >= 0 && LAY <= 2, "tile layout");
+  if (LAY == 1) {
+    const int y = ybase<1>(t);
+    const double2 c = cmul(fac, tab[kWfL1Reg + wf_l1_thr_index(y)]);
+    const double2* tr = tab + wf_l1_reg_index(y);
+#pragma unroll
+    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], cmul(c, tr[r << 1]));
+  } else if (LAY == 2) {
     const double2 c = cmul(fac, tab[t & (kWfTabA - 1)]);
     const double2* tb = tab + kWfTabA + ((t >> 6) & 3);
 #pragma unroll
@@ -49,6 +69,27 @@ __device__ __forceinline__ void wf_diag(double2 (&v)[kRegs], const double2* tab,
     const double2* ta = tab + ((t & 7) << 4);
 #pragma unroll
     for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], cmul(c, ta[r]));
+  }
+}
+
+// Frame-form kick (form B, coefficient f) of tile bit 3 where it is lane bit 3
+// (layouts 1 and 2): the partner amplitude is lane l ^ 8's, one row_ror:8 DPP
+// move per dword, and each lane computes its own row of the butterfly.  RX:
+// S = [[f, i], [i, f]] is symmetric, both lanes run bfly_rx_f<2>'s nu; RY:
+// R = [[f, 1], [-1, f]], the partner enters with the sign of lane bit 3.  The
+// fma shapes are bfly_*_f<2>'s, so the rounding is the register form's.
+template <int KIND>
+__device__ __forceinline__ void wf_kick_lane3(double2 (&v)[kRegs], double f) {
+  const long long sm = (KIND == kKindRY && (__lane_id() & 8)) ? (long long)(1ull << 63) : 0ll;
+#pragma unroll
+  for (int r = 0; r < kRegs; ++r) {
+    const double px = xor_lane<8>(v[r].x), py = xor_lane<8>(v[r].y);
+    if (KIND == kKindRX) {
+      v[r] = make_double2(fma(f, v[r].x, -py), fma(f, v[r].y, px));
+    } else {
+      v[r] = make_double2(fma(f, v[r].x, __longlong_as_double(__double_as_longlong(px) ^ sm)),
+                          fma(f, v[r].y, __longlong_as_double(__double_as_longlong(py) ^ sm)));
+    }
   }
 }
 
@@ -67,6 +108,11 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
   if (b >= A.batch) return;  // the padding states of a last partial octet
   const int inst = (int)((A.batch_start + b) / A.n_traj);
   const int n = A.n_steps;
+  // The column tile (QM0 = 8: nibble 0 holds the one site 11, tile bit 3) never
+  // visits layout 0: bit 3 is lane bit 3 in layouts 1 and 2, so its kick runs
+  // across lanes (wf_kick_lane3) and the odd steps' diagonals are applied in
+  // layout 1 -- two re-layouts per step pair instead of four, all cross-wave.
+  constexpr bool kTwoLay = kWfT2Lay1 && QM0 == 8;
 
   TileMap M;
   M.c = A.c;
@@ -117,6 +163,18 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
 #pragma unroll
     for (int st = 0; st <= kWfSteps; ++st) {
       const int fx = (int)(fxd >> (kTileBits * st)) & (kTile - 1);
+      if (kTwoLay && (st & 1)) {
+        // the layout-1 pair: register table at [0, 64), thread table behind it
+        const bool th = t >= kWfL1Reg;
+        if (t < kWfL1Reg + kWfL1Thr) {
+          const int j = (th ? t - kWfL1Reg : t) ^ (th ? wf_l1_thr_index(fx) : wf_l1_reg_index(fx));
+          const bool neg =
+              st == last && (__popc(j & (th ? wf_l1_thr_zmask(fz) : wf_l1_reg_zmask(fz))) & 1);
+          s_tab[st * kWfTab + (th ? kWfL1Reg : 0) + j] =
+              neg ? make_double2(-stage[st].x, -stage[st].y) : stage[st];
+        }
+        continue;
+      }
       const int j = ti ^ (hi ? fx >> 6 : fx & (kWfTabA - 1));
       const bool neg = st == last && (__popc(j & zt) & 1);
       s_tab[st * kWfTab + (hi ? kWfTabA : 0) + j] =
@@ -143,33 +201,72 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
   using L0 = std::integral_constant<int, 0>;
   using L1 = std::integral_constant<int, 1>;
   using L2 = std::integral_constant<int, 2>;
+  // no flush masks are passed to the re-layouts (the frame's X leaves at the
+  // store), so the 1 <-> 0 pair stays inside each wave (DTC_WF_WAVE_XCH)
+  constexpr bool kWaveXch = DTC_WF_WAVE_XCH != 0;
 
-  bool in0 = false;  // the tile ended in layout 0 (an odd number of steps)
+  // site 11 of the column tile, across lanes (skipped like kick() when the
+  // step's mask leaves it out)
+  auto kick3 = [&](int st) {
+    if (!(A.mask[st] & 8u)) return;
+    const RecScalar R(A.recs + ((int64_t)(st >> 1) * A.batch + b) * kRecPerState);
+    wf_kick_lane3<KIND>(v, R.d((st & 1) * kTileBits + 3, 3));
+  };
+
+  if constexpr (kTwoLay) {
+    bool in1 = false;  // the tile ended in layout 1 (an odd number of steps)
 #pragma unroll 1
-  for (int st = 0; st < n; st += 2) {
-    diag(L2{}, st);
-    kick(L2{}, st);
-    xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
-    kick(L1{}, st);
-    xch_tile<SPLIT, 1, 0>(v, s_tile, s_half, t);
-    kick(L0{}, st);
-    if (st + 1 < n) {
-      diag(L0{}, st + 1);
-      kick(L0{}, st + 1);
-      xch_tile<SPLIT, 0, 1>(v, s_tile, s_half, t);
-      kick(L1{}, st + 1);
-      xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
-      kick(L2{}, st + 1);
-    } else {
-      in0 = true;
+    for (int st = 0; st < n; st += 2) {
+      diag(L2{}, st);
+      kick(L2{}, st);
+      xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
+      kick(L1{}, st);
+      kick3(st);
+      if (st + 1 < n) {
+        diag(L1{}, st + 1);
+        kick3(st + 1);
+        kick(L1{}, st + 1);
+        xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
+        kick(L2{}, st + 1);
+      } else {
+        in1 = true;
+      }
     }
-  }
-  // the trailing kick-less step, then back to the load / store layout
-  if (in0) {
-    diag(L0{}, n);
-    xch_tile<SPLIT, 0, 2>(v, s_tile, s_half, t);
+    // the trailing kick-less step, then back to the load / store layout
+    if (in1) {
+      diag(L1{}, n);
+      xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
+    } else {
+      diag(L2{}, n);
+    }
   } else {
-    diag(L2{}, n);
+    bool in0 = false;  // the tile ended in layout 0 (an odd number of steps)
+#pragma unroll 1
+    for (int st = 0; st < n; st += 2) {
+      diag(L2{}, st);
+      kick(L2{}, st);
+      xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
+      kick(L1{}, st);
+      xch_tile<SPLIT, 1, 0, kWaveXch>(v, s_tile, s_half, t);
+      kick(L0{}, st);
+      if (st + 1 < n) {
+        diag(L0{}, st + 1);
+        kick(L0{}, st + 1);
+        xch_tile<SPLIT, 0, 1, kWaveXch>(v, s_tile, s_half, t);
+        kick(L1{}, st + 1);
+        xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
+        kick(L2{}, st + 1);
+      } else {
+        in0 = true;
+      }
+    }
+    // the trailing kick-less step, then back to the load / store layout
+    if (in0) {
+      diag(L0{}, n);
+      xch_tile<SPLIT, 0, 2>(v, s_tile, s_half, t);
+    } else {
+      diag(L2{}, n);
+    }
   }
   // a launch without any diagonal: the global factor and the frame's Z here
   // (layout 2: the thread's bits 0..7, the registers' 8..11)

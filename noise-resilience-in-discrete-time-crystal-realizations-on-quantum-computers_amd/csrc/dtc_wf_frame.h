@@ -107,5 +107,40 @@ DTC_WF_HD inline void wf_frame_walk(bool rx, int n_steps, const uint32_t* mask, 
   o.ph = ph & 3;
 }
 
+// ---- tile 2's partial diagonal in layout 1 -----------------------------------
+// Tile 2 (tile bits 0..2 = columns, bit k >= 3 = site k + 8) snakes between
+// layouts 2 and 1 only (dtc_wavefront.hip), so the diagonals of its odd steps
+// are applied in layout 1: registers = tile bits 4..7, thread = bits 0..3 and
+// 8..11.  The step's factors regroup into
+//   the register table, 64 entries over tile bits 3..8: everything that touches
+//     a register bit -- fields 4..7, bonds (3,4) .. (7,8) -- read as thread
+//     base (bits 3, 8) + register offset (r << 1);
+//   the thread table, 32 entries over tile bits 3, 8..11: the rest -- field 3
+//     with the outside bond, fields 8..11, bonds (8,9) .. (10,11) -- one
+//     thread-constant entry.
+// Each factor is in exactly one table.  They sit at [0, 64) and [64, 96) of the
+// step's kWfTab-entry slot.  Under the frame both are staged as the 0..6 / 6..11
+// pair is: entry i at i ^ (the frame's X gathered onto the table's index bits),
+// the last diagonal's Z as the parity of the staged index under the gathered Z
+// mask; bits 3 and 8 index both tables and count in the register table only.
+static constexpr int kWfL1Reg = 64;  // register-table entries
+static constexpr int kWfL1Thr = 32;  // thread-table entries
+
+DTC_WF_HD inline bool wf_l1_reg_bit(int k) { return k >= 4 && k <= 7; }
+// position of tile bit k in a table's index, -1 where the table has no such bit
+DTC_WF_HD inline int wf_l1_reg_pos(int k) { return (k >= 3 && k <= 8) ? k - 3 : -1; }
+DTC_WF_HD inline int wf_l1_thr_pos(int k) { return k == 3 ? 0 : ((k >= 8 && k <= 11) ? k - 7 : -1); }
+// a tile index (or an X mask) gathered onto the tables' index bits
+DTC_WF_HD inline int wf_l1_reg_index(int y) { return (y >> 3) & 63; }
+DTC_WF_HD inline int wf_l1_thr_index(int y) { return ((y >> 3) & 1) | (((y >> 8) & 15) << 1); }
+// a Z mask gathered likewise, bits 3 and 8 left to the register table
+DTC_WF_HD inline int wf_l1_reg_zmask(int z) { return (z >> 3) & 63; }
+DTC_WF_HD inline int wf_l1_thr_zmask(int z) { return ((z >> 9) & 7) << 2; }
+// the table of a factor on tile bit k (a field, or a bond to a bit outside the
+// tile: k2 < 0) or on bits k, k2 (a bond inside the tile): true = register
+DTC_WF_HD inline bool wf_l1_in_reg(int k, int k2) {
+  return wf_l1_reg_bit(k) || (k2 >= 0 && wf_l1_reg_bit(k2));
+}
+
 }  // namespace dtc
 #undef DTC_WF_HD
