@@ -12,8 +12,10 @@
 // block's pre / post layer, steps 2, 3 the second's; skipped tile bits carry
 // identity records).  Diagonals: per (instance, step) a 128-entry
 // table over tile bits 0..6 (their fields, the bonds among them) and a 64-entry
-// table over bits 6..11, staged for the workgroup's value of the one index bit
-// outside the tile that a bond reaches (a sign on the in-tile site's angle).
+// table over bits 6..11, for the workgroup's value of the one index bit
+// outside the tile that a bond reaches (a sign on the in-tile site's angle);
+// the table a diagonal reads per register is staged in LDS, the thread's one
+// entry of the other comes straight from the global table.
 // Program: the tile snakes through the register layouts, 2 -> 1 -> 0 in even
 // steps and 0 -> 1 -> 2 in odd ones, so every step costs two LDS re-layouts and
 // the diagonals are applied in layouts 2 and 0 only.  T2's nibble 0 holds the
@@ -24,14 +26,15 @@
 // profiles/r9_wavefront_chain_ab20.txt).  The re-layouts go through
 // a half-tile buffer (exchange_split), so three workgroups share a CU: 8.9 ms
 // per four-layer pass against 10.4 ms with the full tile at two per CU
-// (profiles/r7_wavefront_ab20.txt).
+// (profiles/r7_wavefront_ab20.txt); with the register tables alone beside the
+// buffer and 115 VGPRs tile 1 runs at four per CU (DTC_WF_WG4 below).
 #include <hip/hip_runtime.h>
 
 #include "dtc_device.h"
 #include "dtc_kernels.h"
 #include "dtc_wf_frame.h"
 
-// Three workgroups per CU (half-tile re-layouts) or two (full-tile)
+// Three or four workgroups per CU (half-tile re-layouts) or two (full-tile)
 #ifndef DTC_WF_SPLIT
 #define DTC_WF_SPLIT 1
 #endif
@@ -42,33 +45,40 @@
 #ifndef DTC_WF_WAVE_XCH
 #define DTC_WF_WAVE_XCH 0
 #endif
+// Four workgroups per CU for the half-tile form, bit 0: tile 1, bit 1: the
+// column tile.  The kernels fit either way (at most 128 VGPRs, under 40 KiB of
+// LDS); a tile whose bit is off pads its LDS to stay at three per CU.  The
+// product runs tile 1 at four (8.34 -> 8.01 ms per launch) and the column tile
+// at three (at four it ran 7.41 -> 7.52 ms): C2 +1.8 % against +1.7 % with both
+// at four and +0.0 % with neither (profiles/r10_wavefront_wg4_ab20.txt)
+#ifndef DTC_WF_WG4
+#define DTC_WF_WG4 1
+#endif
 
 namespace dtc {
 
-// v[r] *= fac * TA[..] * TB[..] in layout LAY (2: registers = tile bits 8..11,
-// the 0..6 table is the thread's constant; 0: registers = bits 0..3, the 6..11
-// table is; 1, the column tile's odd steps: registers = bits 4..7, the slot
-// holds the register / thread table pair of dtc_wf_frame.h)
+// v[r] *= (fac * e) * TR[..] in layout LAY: e is the thread's own entry of the
+// table that is constant per thread (fetched from the global table, wf_fetch
+// below), TR the slot's per-register table in LDS.  Layout 2: registers = tile
+// bits 8..11, TR the 6..11 table; 0: registers = bits 0..3, TR the 0..6 table;
+// 1, the column tile's odd steps: registers = bits 4..7, TR the register table
+// of dtc_wf_frame.h.  The table is read four entries at a time with their
+// products in between (a scheduling barrier per group), so the sixteen entries
+// are never all live on top of the tile: the pass fits 128 VGPRs.
 template <int LAY>
-__device__ __forceinline__ void wf_diag(double2 (&v)[kRegs], const double2* tab, int t,
-                                        double2 fac) {
+__device__ __forceinline__ void wf_diag(double2 (&v)[kRegs], const double2* slot, int t,
+                                        double2 fac, double2 e) {
   static_assert(LAY >= 0 && LAY <= 2, "tile layout");
-  if (LAY == 1) {
-    const int y = ybase<1>(t);
-    const double2 c = cmul(fac, tab[kWfL1Reg + wf_l1_thr_index(y)]);
-    const double2* tr = tab + wf_l1_reg_index(y);
+  const double2 c = cmul(fac, e);
+  const double2* tr = slot + (LAY == 1   ? wf_l1_reg_index(ybase<1>(t))
+                              : LAY == 2 ? ((t >> 6) & 3)
+                                         : ((t & 7) << 4));
+  constexpr int kStep = LAY == 1 ? 2 : (LAY == 2 ? 4 : 1);
 #pragma unroll
-    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], cmul(c, tr[r << 1]));
-  } else if (LAY == 2) {
-    const double2 c = cmul(fac, tab[t & (kWfTabA - 1)]);
-    const double2* tb = tab + kWfTabA + ((t >> 6) & 3);
+  for (int g = 0; g < kRegs; g += 4) {
 #pragma unroll
-    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], cmul(c, tb[r << 2]));
-  } else {
-    const double2 c = cmul(fac, tab[kWfTabA + ((t >> 2) & 63)]);
-    const double2* ta = tab + ((t & 7) << 4);
-#pragma unroll
-    for (int r = 0; r < kRegs; ++r) v[r] = cmul(v[r], cmul(c, ta[r]));
+    for (int r = g; r < g + 4; ++r) v[r] = cmul(v[r], cmul(c, tr[r * kStep]));
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -93,13 +103,47 @@ __device__ __forceinline__ void wf_kick_lane3(double2 (&v)[kRegs], double f) {
   }
 }
 
+// LDS keeps the per-register table of every slot only (dtc_wf_frame.h): 64
+// entries for the even slots and the column tile's odd ones, kWfTabA for tile
+// 1's odd ones.  Slot st's offset, and the whole array, in entries:
+__host__ __device__ constexpr int wf_slot_ofs(bool two_lay, int st) {
+  return two_lay ? st * kWfTabB : (st >> 1) * kWfTab + (st & 1) * kWfTabB;
+}
+__host__ __device__ constexpr int wf_tab_lds(bool two_lay) { return wf_slot_ofs(two_lay, kWfSteps + 1); }
+static_assert(kWfTabB == 64 && kWfL1Reg == 64 && kWfTabA == kWfFetchTabA && (kWfSteps & 1) == 0,
+              "the register tables of dtc_wf_frame.h");
+
+// Whether a tile's half-tile form runs at four workgroups per CU: its bit of
+// DTC_WF_WG4, and only where the re-layout buffer and the register tables fit
+// a quarter of the CU's 160 KiB (a development build with the larger additive
+// slots, DTC_ADD_SLOTS, does not, and stays at three)
+__host__ __device__ constexpr bool wf_wg4(int qm0) {
+  return ((DTC_WF_WG4 >> (qm0 == 8)) & 1) &&
+         sizeof(double) * kHalfSlots + sizeof(double2) * wf_tab_lds(kWfT2Lay1 && qm0 == 8) <=
+             160 * 1024 / 4;
+}
+
 template <int KIND, int QM0, bool SPLIT>
-__global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A) {
+__global__ __launch_bounds__(kThreads, SPLIT ? (wf_wg4(QM0) ? 4 : 3) : 2) void dtc_wf_pass(WfArgs A) {
+  constexpr bool kWg4 = SPLIT && wf_wg4(QM0);
+  // The column tile (QM0 = 8: nibble 0 holds the one site 11, tile bit 3) never
+  // visits layout 0: bit 3 is lane bit 3 in layouts 1 and 2, so its kick runs
+  // across lanes (wf_kick_lane3) and the odd steps' diagonals are applied in
+  // layout 1 -- two re-layouts per step pair instead of four, all cross-wave.
+  constexpr bool kTwoLay = kWfT2Lay1 && QM0 == 8;
   // SPLIT: the re-layouts through a half-tile buffer (real parts, then
-  // imaginary parts), so LDS allows three workgroups per CU
+  // imaginary parts); with the register tables alone beside it, 39 936 B
+  // (tile 1) and 37 888 B (the column tile): four workgroups fit a CU's LDS
   __shared__ double2 s_tile[SPLIT ? 1 : kTile];
   __shared__ double s_half[SPLIT ? kHalfSlots : 1];
-  __shared__ double2 s_tab[(kWfSteps + 1) * kWfTab];
+  // A tile that is to stay at three per CU pads s_tab to the full tables'
+  // size, 48 128 B in all.  The padding is dead LDS, there only as an occupancy
+  // limiter: the launch bounds promise a least occupancy, they are no cap, and
+  // the kernel's own 37 888 B and 114 VGPRs would fit a fourth workgroup.
+  // wf_slot_ofs stays the compact one either way.
+  __shared__ double2 s_tab[kWg4 || !SPLIT ? wf_tab_lds(kTwoLay) : (kWfSteps + 1) * kWfTab];
+  static_assert(!kWg4 || sizeof(s_half) + sizeof(s_tab) <= 160 * 1024 / 4, "four workgroups per CU");
+  static_assert(wf_tab_lds(kTwoLay) <= (kWfSteps + 1) * kWfTab, "the padded form holds the tables");
 
   const int t = threadIdx.x;
   const int og = A.octet_bits;
@@ -108,11 +152,8 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
   if (b >= A.batch) return;  // the padding states of a last partial octet
   const int inst = (int)((A.batch_start + b) / A.n_traj);
   const int n = A.n_steps;
-  // The column tile (QM0 = 8: nibble 0 holds the one site 11, tile bit 3) never
-  // visits layout 0: bit 3 is lane bit 3 in layouts 1 and 2, so its kick runs
-  // across lanes (wf_kick_lane3) and the odd steps' diagonals are applied in
-  // layout 1 -- two re-layouts per step pair instead of four, all cross-wave.
-  constexpr bool kTwoLay = kWfT2Lay1 && QM0 == 8;
+  // the layout of the odd slots' diagonals
+  constexpr int kOddLay = kTwoLay ? 1 : 0;
 
   TileMap M;
   M.c = A.c;
@@ -121,14 +162,17 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
   const int mid = A.s - A.c;
   M.tbase = ((tile & (((int64_t)1 << mid) - 1)) << A.c) | ((tile >> mid) << (A.s + kTileBits - A.c));
 
-  // the steps' tables for this workgroup's outside bit, before the tile's loads
+  // the steps' register tables for this workgroup's outside bit, before the
+  // tile's loads
   const int var = A.out_bit >= 0 ? (int)((M.tbase >> A.out_bit) & 1) : 0;
   const double2* tg = A.tab + ((int64_t)inst * (kWfSteps + 1) * 2 + var) * kWfTab;
   double2 stage[kWfSteps + 1];
 #pragma unroll
   for (int st = 0; st <= kWfSteps; ++st) {
+    const int lay = (st & 1) ? kOddLay : 2;
     stage[st] = make_double2(1.0, 0.0);
-    if (t < kWfTab && ((A.dmask >> st) & 1)) stage[st] = tg[st * 2 * kWfTab + t];
+    if (t < wf_reg_size(lay) && ((A.dmask >> st) & 1))
+      stage[st] = tg[st * 2 * kWfTab + wf_reg_base(lay) + t];
   }
 
   const int64_t sbase = state_base(b, A.state_len, og);
@@ -144,40 +188,48 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
     }
   }
   // The Pauli frame of the launch (dtc_wf_frame.h; masks in the second block's
-  // total record): the table of step st is staged X-permuted by the frame's X
-  // at that diagonal -- entry i goes to i ^ x, each table with its part of the
-  // mask -- and the last diagonal's takes the Z flush as a sign per entry (a
-  // parity of the staged index; tile bit 6 counts in the 6..11 table).  Done at
-  // the LDS write, so the scalar loads of the masks wait behind the tile's
-  // loads, not in front of them.
+  // total record): the tables of step st are read X-permuted by the frame's X
+  // at that diagonal -- entry i ^ x at i, each table with its part of the mask
+  // -- and the last diagonal's take the Z flush as a sign per entry (a parity
+  // of the index read; tile bit 6 counts in the 6..11 table).  The register
+  // tables are staged so, at the LDS write, and the thread's own entries are
+  // fetched so (wf_fetch): the scalar loads of the masks wait behind the
+  // tile's loads, not in front of them.
   const RecScalar R0(A.recs + b * kRecPerState);
   const RecScalar R1(A.recs + ((int64_t)A.batch + b) * kRecPerState);
   const long long fxd = R1.bits(8 * kRecTotal + kWfMaskXD);
   const int fzx = R1.i(kRecTotal, kWfMaskZX);
-  if (t < kWfTab) {
-    const int last = 31 - __builtin_clz(A.dmask | 1);
+  const int last = 31 - __builtin_clz(A.dmask | 1);
+  // The entry of step st's per-thread table that this thread multiplies by,
+  // from the global table (1 where the step has no diagonal).  Fetched one
+  // diagonal ahead, so one entry is live at a time and its latency hides
+  // behind the kicks and re-layouts in between.
+  auto wf_fetch = [&](auto lay, int st) {
+    constexpr int LAY = decltype(lay)::value;
+    double2 e = make_double2(1.0, 0.0);
+    if ((A.dmask >> st) & 1) {
+      const int fx = (int)(fxd >> (kTileBits * st)) & (kTile - 1);
+      e = tg[st * 2 * kWfTab + wf_thr_fetch(LAY, ybase<LAY>(t), fx)];
+      if (st == last && wf_thr_neg(LAY, ybase<LAY>(t), fzx & (kTile - 1)))
+        e = make_double2(-e.x, -e.y);
+    }
+    return e;
+  };
+  using L0 = std::integral_constant<int, 0>;
+  using L1 = std::integral_constant<int, 1>;
+  using L2 = std::integral_constant<int, 2>;
+  using LOdd = std::integral_constant<int, kOddLay>;
+  double2 cn = wf_fetch(L2{}, 0);
+  if (t < kWfTabA) {
     const int fz = fzx & (kTile - 1);
-    const bool hi = t >= kWfTabA;
-    const int ti = hi ? t - kWfTabA : t;
-    const int zt = hi ? fz >> 6 : fz & 63;
 #pragma unroll
     for (int st = 0; st <= kWfSteps; ++st) {
+      const int lay = (st & 1) ? kOddLay : 2;
+      if (t >= wf_reg_size(lay) || !((A.dmask >> st) & 1)) continue;
       const int fx = (int)(fxd >> (kTileBits * st)) & (kTile - 1);
-      if (kTwoLay && (st & 1)) {
-        // the layout-1 pair: register table at [0, 64), thread table behind it
-        const bool th = t >= kWfL1Reg;
-        if (t < kWfL1Reg + kWfL1Thr) {
-          const int j = (th ? t - kWfL1Reg : t) ^ (th ? wf_l1_thr_index(fx) : wf_l1_reg_index(fx));
-          const bool neg =
-              st == last && (__popc(j & (th ? wf_l1_thr_zmask(fz) : wf_l1_reg_zmask(fz))) & 1);
-          s_tab[st * kWfTab + (th ? kWfL1Reg : 0) + j] =
-              neg ? make_double2(-stage[st].x, -stage[st].y) : stage[st];
-        }
-        continue;
-      }
-      const int j = ti ^ (hi ? fx >> 6 : fx & (kWfTabA - 1));
-      const bool neg = st == last && (__popc(j & zt) & 1);
-      s_tab[st * kWfTab + (hi ? kWfTabA : 0) + j] =
+      const int j = t ^ wf_reg_xmask(lay, fx);
+      const bool neg = st == last && (__popc(j & wf_reg_zmask(lay, fz)) & 1);
+      s_tab[wf_slot_ofs(kTwoLay, st) + j] =
           neg ? make_double2(-stage[st].x, -stage[st].y) : stage[st];
     }
   }
@@ -187,10 +239,15 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
   // the second), folded into the first diagonal applied
   double2 gf = cmul(make_double2(R0.d(kRecTotal, 0), R0.d(kRecTotal, 1)),
                     make_double2(R1.d(kRecTotal, 0), R1.d(kRecTotal, 1)));
-  auto diag = [&](auto lay, int st) {
-    if (!((A.dmask >> st) & 1)) return;
-    wf_diag<decltype(lay)::value>(v, s_tab + st * kWfTab, t, gf);
-    gf = make_double2(1.0, 0.0);
+  // the diagonal before step st with the entry fetched for it; then the fetch
+  // for the next one, slot nx in layout nlay (the next step's or the trailing
+  // one; past those dmask has no bit)
+  auto diag = [&](auto lay, int st, auto nlay, int nx) {
+    if ((A.dmask >> st) & 1) {
+      wf_diag<decltype(lay)::value>(v, s_tab + wf_slot_ofs(kTwoLay, st), t, gf, cn);
+      gf = make_double2(1.0, 0.0);
+    }
+    if (nx <= kWfSteps) cn = wf_fetch(nlay, nx);
   };
   auto kick = [&](auto nib, int st) {
     constexpr int N = decltype(nib)::value;
@@ -198,9 +255,6 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
     const RecScalar R(A.recs + ((int64_t)(st >> 1) * A.batch + b) * kRecPerState);
     apply_nibble<N, KIND, N == 0 ? QM0 : 15, /*FRAME=*/true>(v, R, (st & 1) * kTileBits);
   };
-  using L0 = std::integral_constant<int, 0>;
-  using L1 = std::integral_constant<int, 1>;
-  using L2 = std::integral_constant<int, 2>;
   // no flush masks are passed to the re-layouts (the frame's X leaves at the
   // store), so the 1 <-> 0 pair stays inside each wave (DTC_WF_WAVE_XCH)
   constexpr bool kWaveXch = DTC_WF_WAVE_XCH != 0;
@@ -213,61 +267,44 @@ __global__ __launch_bounds__(kThreads, SPLIT ? 3 : 2) void dtc_wf_pass(WfArgs A)
     wf_kick_lane3<KIND>(v, R.d((st & 1) * kTileBits + 3, 3));
   };
 
-  if constexpr (kTwoLay) {
-    bool in1 = false;  // the tile ended in layout 1 (an odd number of steps)
+  // The trailing kick-less step runs as the loop's own diagonal of its parity
+  // (one copy of each diagonal in the code, and the tile stays in the loop's
+  // registers: a second copy behind the loop cost 112 B per lane of scratch at
+  // 128 VGPRs); a pass with an odd step count then leaves the loop in the odd
+  // slots' layout and goes back to the load / store layout behind it.
+  // (a bottom-tested loop: rotating a top-tested one would clone the first
+  // diagonal in front of it again)
+  int st = 0;
 #pragma unroll 1
-    for (int st = 0; st < n; st += 2) {
-      diag(L2{}, st);
+  do {
+    diag(L2{}, st, LOdd{}, st + 1);
+    if (st < n) {
       kick(L2{}, st);
       xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
       kick(L1{}, st);
-      kick3(st);
+      if constexpr (kTwoLay) {
+        kick3(st);
+      } else {
+        xch_tile<SPLIT, 1, 0, kWaveXch>(v, s_tile, s_half, t);
+        kick(L0{}, st);
+      }
+      diag(LOdd{}, st + 1, L2{}, st + 2);
       if (st + 1 < n) {
-        diag(L1{}, st + 1);
-        kick3(st + 1);
-        kick(L1{}, st + 1);
+        if constexpr (kTwoLay) {
+          kick3(st + 1);
+          kick(L1{}, st + 1);
+        } else {
+          kick(L0{}, st + 1);
+          xch_tile<SPLIT, 0, 1, kWaveXch>(v, s_tile, s_half, t);
+          kick(L1{}, st + 1);
+        }
         xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
         kick(L2{}, st + 1);
-      } else {
-        in1 = true;
       }
     }
-    // the trailing kick-less step, then back to the load / store layout
-    if (in1) {
-      diag(L1{}, n);
-      xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
-    } else {
-      diag(L2{}, n);
-    }
-  } else {
-    bool in0 = false;  // the tile ended in layout 0 (an odd number of steps)
-#pragma unroll 1
-    for (int st = 0; st < n; st += 2) {
-      diag(L2{}, st);
-      kick(L2{}, st);
-      xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
-      kick(L1{}, st);
-      xch_tile<SPLIT, 1, 0, kWaveXch>(v, s_tile, s_half, t);
-      kick(L0{}, st);
-      if (st + 1 < n) {
-        diag(L0{}, st + 1);
-        kick(L0{}, st + 1);
-        xch_tile<SPLIT, 0, 1, kWaveXch>(v, s_tile, s_half, t);
-        kick(L1{}, st + 1);
-        xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
-        kick(L2{}, st + 1);
-      } else {
-        in0 = true;
-      }
-    }
-    // the trailing kick-less step, then back to the load / store layout
-    if (in0) {
-      diag(L0{}, n);
-      xch_tile<SPLIT, 0, 2>(v, s_tile, s_half, t);
-    } else {
-      diag(L2{}, n);
-    }
-  }
+    st += 2;
+  } while (st <= n);
+  if (n & 1) xch_tile<SPLIT, kOddLay, 2>(v, s_tile, s_half, t);
   // a launch without any diagonal: the global factor and the frame's Z here
   // (layout 2: the thread's bits 0..7, the registers' 8..11)
   if (!A.dmask) {

@@ -142,5 +142,48 @@ DTC_WF_HD inline bool wf_l1_in_reg(int k, int k2) {
   return wf_l1_reg_bit(k) || (k2 >= 0 && wf_l1_reg_bit(k2));
 }
 
+// ---- the thread's own table entry, fetched from the global table --------------
+// A diagonal reads one of its slot's two tables per register and the other
+// once per thread (dtc_wavefront.hip, wf_diag).  Only the per-register table is
+// staged in LDS; the thread takes its constant straight from the slot's global
+// table (kWfTabA + kWfTabB entries as wf_table_set fills them), applying the
+// staging's X permutation and Z sign itself: with i the thread's index into
+// the staged table, the entry is global[i ^ x] (x = the step's frame X gathered
+// onto the table's index bits), negated in the last diagonal by the parity of i
+// under the gathered Z mask -- the value a staged table holds at i.
+// lay: the layout the diagonal runs in (2: even slots; 0: tile 1's odd slots;
+// 1: tile 2's odd slots); y: the thread's tile index base, ybase<lay>(t).
+static constexpr int kWfFetchTabA = 128;  // kWfTabA
+DTC_WF_HD inline int wf_thr_staged(int lay, int y) {
+  return lay == 2 ? (y & (kWfFetchTabA - 1)) : (lay == 0 ? ((y >> 6) & 63) : wf_l1_thr_index(y));
+}
+// offset of the thread's entry in the slot's global table under the frame X fx
+DTC_WF_HD inline int wf_thr_fetch(int lay, int y, int fx) {
+  const int i = wf_thr_staged(lay, y);
+  if (lay == 2) return i ^ (fx & (kWfFetchTabA - 1));
+  if (lay == 0) return kWfFetchTabA + (i ^ ((fx >> 6) & 63));
+  return kWfL1Reg + (i ^ wf_l1_thr_index(fx));
+}
+// the last diagonal's sign of that entry under the frame Z fz (tile bit 6, and
+// in layout 1 bits 3 and 8, count in the other table)
+DTC_WF_HD inline bool wf_thr_neg(int lay, int y, int fz) {
+  const int zm = lay == 2 ? (fz & 63) : (lay == 0 ? ((fz >> 6) & 63) : wf_l1_thr_zmask(fz));
+  int p = wf_thr_staged(lay, y) & zm;
+  p ^= p >> 4;
+  p ^= p >> 2;
+  p ^= p >> 1;
+  return p & 1;
+}
+// The per-register table of a slot, the one LDS keeps: its offset and size in
+// the slot's global table, and the X / Z masks gathered onto its index.
+DTC_WF_HD inline int wf_reg_base(int lay) { return lay == 2 ? kWfFetchTabA : 0; }
+DTC_WF_HD inline int wf_reg_size(int lay) { return lay == 0 ? kWfFetchTabA : 64; }
+DTC_WF_HD inline int wf_reg_xmask(int lay, int fx) {
+  return lay == 2 ? ((fx >> 6) & 63) : (lay == 0 ? (fx & (kWfFetchTabA - 1)) : wf_l1_reg_index(fx));
+}
+DTC_WF_HD inline int wf_reg_zmask(int lay, int fz) {
+  return lay == 2 ? ((fz >> 6) & 63) : (lay == 0 ? (fz & 63) : wf_l1_reg_zmask(fz));
+}
+
 }  // namespace dtc
 #undef DTC_WF_HD

@@ -9,7 +9,10 @@
 //             X (and the last one's signed by its Z), i^ph on the whole tile,
 //             the X flush at the store (index y written to y ^ x),
 // and the two tiles must agree to 1e-12 (both scaled by the kicks' common
-// 1 / sqrt(1 + coef^2), so the tile keeps norm 1).
+// 1 / sqrt(1 + coef^2), so the tile keeps norm 1).  The kernel stages only a
+// slot's per-register table and has each thread fetch its own entry of the
+// other table from the global one (wf_thr_fetch, wf_thr_neg, wf_reg_*): every
+// such entry must equal the fully staged table's, bit for bit.
 // Cases: RX and RY; tile 1 (all 12 bits are sites) and tile 2 (bits 0..2 are
 // columns, never kicked); 1..4 steps, with and without the trailing diagonal,
 // with and without the diagonal before step 0 (a pass that enters with that
@@ -116,7 +119,10 @@ void for_step_bits(const Case& c, int st, F fn) {
   }
 }
 
-double run_case(const Case& c, std::mt19937_64& rng) {
+// fetch_fails: this case's direct-fetch / register-table entries that differ
+// from the staged ones
+double run_case(const Case& c, std::mt19937_64& rng, long& fetch_fails) {
+  fetch_fails = 0;
   std::normal_distribution<double> nd;
   std::vector<cd> psi(NT);
   double nrm = 0.0;
@@ -152,6 +158,26 @@ double run_case(const Case& c, std::mt19937_64& rng) {
         const int zt = hi ? fr.zlast >> 6 : fr.zlast & 63;
         const bool neg = st == last && (__builtin_popcount(j & zt) & 1);
         stg[(hi ? kTabA : 0) + j] = neg ? -c.tab[st][t] : c.tab[st][t];
+      }
+      // dtc_wf_pass keeps only the slot's per-register table in LDS and each
+      // thread fetches its own entry of the other from the global table
+      // (wf_thr_fetch / wf_thr_neg): both must be the staged values, bit for
+      // bit, in layout 2 (even slots) and in layout 0 (tile 1's odd slots; the
+      // column tile's layout-1 pair: tools/wavefront_lay1_check.cpp)
+      const int lay = (st & 1) ? 0 : 2;
+      for (int t = 0; t < 256; ++t) {
+        const int y = lay == 2 ? t : t << 4;  // ybase<lay>(t)
+        cd e = c.tab[st][dtc::wf_thr_fetch(lay, y, x)];
+        if (st == last && dtc::wf_thr_neg(lay, y, fr.zlast)) e = -e;
+        const cd want = lay == 2 ? stg[y & (kTabA - 1)] : stg[kTabA + (y >> 6)];
+        if (e != want) ++fetch_fails;
+      }
+      for (int i = 0; i < dtc::wf_reg_size(lay); ++i) {
+        const int j = i ^ dtc::wf_reg_xmask(lay, x);
+        const bool neg =
+            st == last && (__builtin_popcount(j & dtc::wf_reg_zmask(lay, fr.zlast)) & 1);
+        const cd e = c.tab[st][dtc::wf_reg_base(lay) + i];
+        if ((neg ? -e : e) != stg[dtc::wf_reg_base(lay) + j]) ++fetch_fails;
       }
       for (int y = 0; y < NT; ++y) got[y] *= stg[y & (kTabA - 1)] * stg[kTabA + (y >> 6)];
     }
@@ -210,9 +236,16 @@ int main() {
                 }
               }
               for (int st = 0; st <= NS; ++st) c.tab[st] = make_tables(rng, c.out);
-              const double err = run_case(c, rng);
+              long fetch_fails = 0;
+              const double err = run_case(c, rng, fetch_fails);
               ++n_cases;
               if (err > worst) worst = err;
+              if (fetch_fails) {
+                std::printf("FAIL rx %d tile %d steps %d dmask %d masks %d seed %d: %ld fetched "
+                            "table entries differ from the staged ones\n", rx, tile, n_steps,
+                            c.dmask, mk, seed, fetch_fails);
+                return 1;
+              }
               if (!(err < 1e-12)) {
                 std::printf("FAIL rx %d tile %d steps %d dmask %d masks %d seed %d: %.3e\n", rx,
                             tile, n_steps, c.dmask, mk, seed, err);

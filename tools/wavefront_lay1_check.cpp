@@ -11,7 +11,11 @@
 //  2. staged under a frame -- entry i at i ^ (X gathered onto the table's index
 //     bits), signed by the parity of the staged index under the gathered Z mask
 //     -- a lookup at y gives (-1)^|y & z| D(y ^ x), exactly for the pair's own
-//     product and to 1e-14 against the three-layout form staged its way;
+//     product and to 1e-14 against the three-layout form staged its way; and
+//     the kernel's split of every slot -- register table staged, the thread's
+//     entry of the other table fetched from the global slot with the XOR and
+//     the sign applied by the thread -- reproduces those staged tables exactly,
+//     in layouts 2, 1 and 0;
 //  3. the two-layout program (2 -> 1 in even steps, 1 -> 2 in odd ones, bit 3
 //     kicked as an ordinary butterfly: across lanes it is the same fma per
 //     amplitude) against the three-layout snake on a 12-bit tile: bit for bit
@@ -186,6 +190,33 @@ int main() {
         const double e = dist(got, old);
         worst_stage = std::fmax(worst_stage, e);
         want(e < 1e-14, "staged layout-1 pair != staged 0..6 x 6..11 pair", seed, e);
+      }
+      // the kernel's split of a slot: the per-register table staged in LDS
+      // (wf_reg_*), the thread's own entry of the other fetched from the
+      // slot's global table (wf_thr_fetch / wf_thr_neg) -- both are the staged
+      // values above, bit for bit, in all three layouts
+      auto same = [](c2 a, c2 b) { return a.x == b.x && a.y == b.y; };
+      for (int lay = 0; lay < 3; ++lay) {
+        std::vector<c2> slot = lay == 1 ? tr : ta;  // the slot as wf_table_set fills it
+        const std::vector<c2>& second = lay == 1 ? tt : tb;
+        slot.insert(slot.end(), second.begin(), second.end());
+        const std::vector<c2>& sreg = lay == 1 ? sr : (lay == 2 ? sb : sa);
+        for (int t = 0; t < 256; ++t) {
+          const int y = lay == 2 ? t : (lay == 1 ? ((t & 15) | ((t >> 4) << 8)) : t << 4);
+          c2 e = slot[dtc::wf_thr_fetch(lay, y, fx)];
+          if (dtc::wf_thr_neg(lay, y, fz)) e = {-e.x, -e.y};
+          const c2 ref = lay == 1   ? st[dtc::wf_l1_thr_index(y)]
+                         : lay == 2 ? sa[y & (kTabA - 1)]
+                                    : sb[y >> 6];
+          want(same(e, ref), "fetched thread entry != staged thread table", seed, dist(e, ref));
+        }
+        want((int)sreg.size() == dtc::wf_reg_size(lay), "register table size", seed, lay);
+        for (int i = 0; i < dtc::wf_reg_size(lay); ++i) {
+          const int j = i ^ dtc::wf_reg_xmask(lay, fx);
+          c2 e = slot[dtc::wf_reg_base(lay) + i];
+          if (parity(j & dtc::wf_reg_zmask(lay, fz))) e = {-e.x, -e.y};
+          want(same(e, sreg[j]), "staged register table != staged table", seed, dist(e, sreg[j]));
+        }
       }
     }
 
