@@ -58,7 +58,8 @@ $(OBJDIR)/dtc_wavefront.o: $(PKG)/csrc/dtc_wavefront.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
 
-$(OBJDIR)/dtc_engine.o: $(PKG)/csrc/dtc_engine.cpp $(HDRS)
+# (the schedule header is host code of the engine alone: the kernels do not see it)
+$(OBJDIR)/dtc_engine.o: $(PKG)/csrc/dtc_engine.cpp $(PKG)/csrc/dtc_schedule.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
 
@@ -74,12 +75,12 @@ $(ORACLE): oracle/dtc_oracle.c
 $(ORACLE3): oracle/dtc_oracle.c
 	$(CC) -O3 -march=x86-64-v3 -fopenmp -fPIC -shared -std=c11 -Wall $< -o $@ -lm
 
-resource-usage: $(SRCS) $(HDRS)
+resource-usage: $(SRCS) $(HDRS) $(PKG)/csrc/dtc_schedule.h
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage $(SRCS) -o /tmp/dtc_ru.so
 
 # Development-only build (instrumentation; never the product): per-workgroup
 # phase timing, loaded with DTC_LIB=build/libdtc_timing.so by tools/phase_timing.py.
-build/libdtc_timing.so: $(SRCS) $(HDRS)
+build/libdtc_timing.so: $(SRCS) $(HDRS) $(PKG)/csrc/dtc_schedule.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -DDTC_PHASE_TIMING=3 $(SRCS) -o $@
 

@@ -30,8 +30,11 @@
 #include "../../include/dtc.h"
 #include "dtc_kernels.h"
 #include "dtc_rng.h"
+#include "dtc_schedule.h"
 #include "dtc_wavefront.h"
 #include "dtc_wf_frame.h"
+
+using namespace dtc::sched;
 
 namespace {
 
@@ -68,13 +71,6 @@ struct HostBuf {
   size_t n = 0;  // doubles
 };
 
-
-struct Group {
-  int c, s;  // tile = bits [0, c) + [s, s + tb - c)
-  int act;   // active tile-bit mask
-  int tb = dtc::kTileBits;  // tile bits: 12, or 13 (the 13-site group, dtc_tile13.hip)
-};
-
 struct Pending {
   int kind;
   hipEvent_t e0, e1;
@@ -106,13 +102,11 @@ struct dtc_ctx {
   bool prof = false;
   // options fixed at dtc_open (environment read once there; development A/B
   // switches, documented in DESIGN.md): batch state layout, light-cone pass
-  // variant, the basis-synthesising first pass, the light-cone merge, batch
-  // memory budget, verbose batch report
+  // variant, the basis-synthesising first pass, batch memory budget, verbose
+  // batch report; the scheduling options are `so` below
   int octet_bits = 6;        // DTC_OCTET_BITS (0 = contiguous states)
   int lc_split = 1;          // DTC_LC_SPLIT
   int lc_tpb = 0;            // DTC_LC_TPB (0 = default)
-  bool lc_wide = true;       // DTC_NO_LCW unset: five-pass (10-site) light-cone ends
-  bool lc_wide3 = true;      // DTC_NO_LCW3 unset: six-pass (12-site) ends where they fit
   HostBuf host_f, host_e;    // pinned result staging (autocorr / energy)
   uint64_t tables_key = 0;   // upload_tables: the problem whose tables are in place
   bool tables_valid = false;
@@ -120,25 +114,13 @@ struct dtc_ctx {
   // PassArgs::kdk_split): the 12-site probe passes, every per-site/energy pass
   int kdk_split = (1 << 7) | (1 << (8 + 7)) | (1 << (8 + 6));
   bool basis_synth = true;   // DTC_NO_BASIS_SYNTH
-  bool lightcone = true;     // DTC_NO_LIGHTCONE
   double batch_bytes = 0.0;  // DTC_BATCH_BYTES (0 = automatic)
   bool verbose = false;      // DTC_VERBOSE
   int prefix_octet = 0;      // layout the prefix states were built in
   int64_t st_n[DTC_KERNEL_KINDS] = {};
   int64_t lc_launches[4] = {};  // light-cone passes by kernel (dtc_lightcone_counts)
-  bool dual = true;  // DTC_NO_DUAL: echo chains start with a pass of their own
-  bool runahead = true;  // DTC_NO_RUNAHEAD: device-noise forward closes periods with K-D
-  // DTC_SPLIT13=1: L = 20 sweeps run the 13 / 7 site groups (round 6: built
-  // and parity-tested, slower than the 12 / 8 split on the power-capped chip,
-  // profiles/r6q_*; the 12 / 8 split stays the default)
-  bool split13 = false;
+  SchedOpts so;  // the scheduling options (dtc_schedule.h)
   int64_t sched_counts[4] = {};  // dtc_schedule_counts: folds, run-ahead, rebuilt, 13 / 7
-  // Wavefront interior of the echo chains (dtc_wavefront.h, dtc_wavefront.hip):
-  // on by default (profiles/r7_wavefront_ab20.txt: C2 +5.4 %);
-  // DTC_NO_WAVEFRONT=1 keeps the plain K-D-K interior, DTC_WAVEFRONT=2..4 sets
-  // the layer cap per pass (4: the measured best)
-  bool wavefront = true;
-  int wf_cap = dtc::kWfSteps;
   int64_t wf_launches = 0;       // dtc_wavefront_count
   DevBuf wf_tab;                 // the partial-diagonal table sets of the current problem
   double st_ms[DTC_KERNEL_KINDS] = {};
@@ -222,79 +204,6 @@ int settle_pending(dtc_ctx* ctx) {
   return ctx->pending.size() > 16384 ? resolve_pending(ctx) : DTC_OK;
 }
 
-struct Plan {
-  int L = 0, L_eff = 0, n_chunks = 0, n_tiles = 0, diag_stride = 0;
-  int64_t len = 0;
-  std::vector<Group> groups;
-};
-
-// Site groups: group 0 = sites [0, a0) in a contiguous 4096-amplitude tile;
-// further groups take up to `hi_max` sites each (tile = 12 - a column bits of
-// >= 128-B rows + the group's sites).  Defaults: 11 + 9 for L = 20.
-// Site groups: the low group (tile bits 0..11 = sites 0..a_lo-1) and higher
-// groups of a sites each (tile = a_lo.. column bits 0..c-1 + the group's a
-// sites, c = 12 - a).  Sizes are chosen so that the register nibble the
-// diagonal is applied in never straddles the column boundary c (kernel
-// diag_in: one window-table lookup per amplitude): the low group holds 9..12
-// sites, a higher group 9, 8 or 4 (c = 3, 4, 8).  Fewest groups first, then
-// the largest low group, then the largest higher groups.
-// largest_top (sharded states): the high groups in increasing size, so the
-// group holding the top bits (the bits an exchange swaps with the rank bits)
-// is a large one and the pre-exchange kicks stay below a few free bits of it
-// (the slices of dtc_shard_kick_slice).
-// split13 (round 6, L = 20 only): a 13-site group at tile bits 0..12
-// (dtc_tile13.hip) and a 7-site column group, tile bits 0..4 + sites 13..19
-// (pass_body kGeoB7) -- the column pass kicks 7 sites over 512-B runs instead
-// of 8 over 256-B runs (tools/tile13_kdk_probe.hip, profiles/r6c_*).
-// pl.n_tiles is then the larger group's tile count (buffer sizes); a pass's
-// own is 2^(L_eff - tb).
-Plan make_plan(int L, bool largest_top = false, bool split13 = false) {
-  Plan pl;
-  pl.L = L;
-  pl.L_eff = std::max(L, dtc::kTileBits);
-  pl.len = (int64_t)1 << pl.L_eff;
-  pl.n_tiles = 1 << (pl.L_eff - dtc::kTileBits);
-  pl.n_chunks = (pl.L_eff + dtc::kChunkBits - 1) / dtc::kChunkBits;
-  pl.diag_stride = (pl.n_chunks + pl.L_eff) * 64;
-  if (split13 && L == 20) {
-    pl.groups.push_back(Group{dtc::kMaxTileBits, dtc::kMaxTileBits, (1 << dtc::kMaxTileBits) - 1,
-                              dtc::kMaxTileBits});
-    pl.groups.push_back(Group{dtc::kB7Cols, dtc::kMaxTileBits, 0xFE0, dtc::kTileBits});
-    return pl;
-  }
-  if (L <= dtc::kTileBits) {
-    // one group; the padding sites L..11 get identity kicks (kernel) so the
-    // whole 12-bit tile runs the standard round plan
-    pl.groups.push_back(Group{0, 0, (1 << dtc::kTileBits) - 1});
-    return pl;
-  }
-  static const int kHi[3] = {9, 8, 4};
-  for (int n_hi = (L - dtc::kTileBits + 8) / 9;; ++n_hi) {
-    for (int a_lo = dtc::kTileBits; a_lo >= 9; --a_lo) {
-      const int need = L - a_lo;
-      // n9 nines, n8 eights, the rest fours
-      for (int n9 = n_hi; n9 >= 0; --n9) {
-        for (int n8 = n_hi - n9; n8 >= 0; --n8) {
-          const int n4 = n_hi - n9 - n8;
-          if (9 * n9 + 8 * n8 + 4 * n4 != need) continue;
-          pl.groups.push_back(Group{0, 0, (1 << a_lo) - 1});
-          int s = a_lo;
-          for (int kk = 0; kk < 3; ++kk) {
-            const int k = largest_top ? 2 - kk : kk;
-            const int cnt = k == 0 ? n9 : (k == 1 ? n8 : n4);
-            for (int i = 0; i < cnt; ++i) {
-              const int a = kHi[k], c = dtc::kTileBits - a;
-              pl.groups.push_back(Group{c, s, ((1 << a) - 1) << c});
-              s += a;
-            }
-          }
-          return pl;
-        }
-      }
-    }
-  }
-}
-
 // Diagonal factor tables (RZZ even/odd bonds + RZ, fast.py:115-120):
 // D(x) = exp(-i/2 (sum_i h_i z_i + sum_i phi_i z_i z_{i+1})), z_i = 1 - 2 bit_i(x).
 // Per instance: n_chunks chunk tables, D(x) = prod_k C_k[(x >> 5k) & 63] (C_k covers
@@ -338,125 +247,6 @@ void build_diag_tables(const Plan& pl, int n_inst, const double* h, const double
       }
     }
   }
-}
-
-struct RunCfg {
-  const dtc_problem* prob;
-  Plan pl;
-  std::vector<int> row_kind;  // KickKind of every kick-table row
-  uint64_t seed;
-  int64_t traj_offset;
-  int n_traj;
-  int noisy;
-  uint32_t thr1, thr2, thr3;
-  const int* site_of = nullptr;  // device: physical bit -> logical site (shards)
-  int octet_bits = 0;            // batch state layout (dtc_kernels.h state_base)
-  // sharded state: the tables live in ctx->shard_cache / shard_kick, and a
-  // chunk pass covers the low L_eff_override bits of states stride_override apart
-  const double2* diag_tab = nullptr;
-  const double2* kick_tab = nullptr;
-  int L_eff_override = 0;
-  int64_t stride_override = 0;
-  // device-like noise (dtc_autocorr_device): general non-unitary kicks, no
-  // forward pass runs ahead of a branch point (a jump cannot be undone)
-  bool device = false;
-  std::vector<uint32_t> dev_thr_host;  // [L][3] per-site Pauli thresholds (prep X)
-  const uint32_t* dev_thr = nullptr;   // device copies
-  const uint32_t* dev_jump = nullptr;
-  const double* dev_kraus = nullptr;
-  // two-qubit depolarizing noise on the bonds (dtc_autocorr_bond): thresholds of
-  // sample_bond per bond (host and device), the instances' angles on the device
-  bool bond = false;
-  std::vector<uint32_t> bond_thr_host;
-  const uint32_t* bond_thr = nullptr;
-  const double* bond_h = nullptr;
-  const double* bond_phi = nullptr;
-};
-
-// ---- layer chains ---------------------------------------------------------
-using dtc::KickDesc;
-
-KickDesc no_kick() { return KickDesc{0, 0, 0, 0u, 0u}; }
-
-struct Chain {
-  std::vector<KickDesc> X;  // kick layers X_0..X_n
-  bool trailing_d = false;  // a D after X_n too
-  int diag = dtc::kDiagFwd;
-  std::vector<int> kc;      // layers applied per group
-  int nd = 0;               // diagonals applied
-  bool post_after_d = true; // a pass that applies D may start the next layer
-  std::vector<int> prio;    // tie-break between groups with equal kc (lower first); empty = index
-  int n() const { return (int)X.size() - 1; }
-  int n_d() const { return trailing_d ? n() + 1 : n(); }
-  bool done() const {
-    if (nd != n_d()) return false;
-    for (int k : kc)
-      if (k != n() + 1) return false;
-    return true;
-  }
-};
-
-struct PassSpec {
-  int group;
-  KickDesc pre, post;
-  int diag;    // DiagMode
-  int d_index; // diagonals applied after this pass (valid when diag)
-  // light-cone end of an echo chain (kShapeLC): tile = bits 0..3 + sites
-  // lc_w0..lc_w0+7; layers lc[0] D* lc[1] ... D* lc[lc_layers-1] on the window
-  // sites of lc_mask (bit 8 l + b: site lc_w0 + b in layer l), then the probe
-  int lc_w0 = -1;
-  int lc_layers = 0;
-  KickDesc lc[dtc::kLcMaxLayers] = {};
-  uint64_t lc_mask = 0;
-  // the 10-site form (lc_merge_wide): tile bit k = global bit lc_gb[k], lc_mask
-  // bit 10 l + k - 2 = tile bit k kicked in layer l
-  int lc_wide = 0;
-  int8_t lc_gb[dtc::kTileBits] = {};
-  // the 12-site form (lc_wide = 2, lc_merge_wide7): tile bit k = global bit
-  // j-5+k, bit 12 l + k of the 84-bit mask lc_mask | lc_mask2 << 64
-  uint64_t lc_mask2 = 0;
-};
-
-// the tile bits a light-cone pass kicks in layer l (nonzero: the layer runs)
-uint64_t lc_layer_bits(const PassSpec& ps, int l) {
-  if (ps.lc_wide == 2) {
-    uint64_t m = 0;
-    for (int k = 0; k < dtc::kTileBits; ++k) {
-      const int bit = 12 * l + k;
-      const uint64_t on = bit < 64 ? (ps.lc_mask >> bit) & 1ull : (ps.lc_mask2 >> (bit - 64)) & 1ull;
-      m |= on << k;
-    }
-    return m;
-  }
-  return ps.lc_wide ? (ps.lc_mask >> (10 * l)) & 0x3FFull
-                    : (ps.lc_mask >> (dtc::kLcSites * l)) & 0xFFull;
-}
-
-// The tile geometry of a pass (the plan's group, or the light-cone window).
-Group pass_group(const Plan& pl, const PassSpec& ps) {
-  if (ps.lc_w0 >= 0) return Group{4, ps.lc_w0, 0xFF0};
-  return pl.groups[ps.group];
-}
-
-// Emit the next pass of a chain (greedy, deterministic).
-PassSpec next_pass(Chain& ch) {
-  int G = 0;
-  for (int g = 1; g < (int)ch.kc.size(); ++g) {
-    const int pg = ch.prio.empty() ? g : ch.prio[g], pG = ch.prio.empty() ? G : ch.prio[G];
-    if (ch.kc[g] < ch.kc[G] || (ch.kc[g] == ch.kc[G] && pg < pG)) G = g;
-  }
-  PassSpec ps{G, no_kick(), no_kick(), dtc::kDiagNone, ch.nd};
-  const int n = ch.n();
-  if (ch.kc[G] == ch.nd && ch.kc[G] <= n) ps.pre = ch.X[ch.kc[G]++];
-  bool level = true;
-  for (int k : ch.kc)
-    if (k != ch.nd + 1) level = false;
-  if (level && ch.nd < ch.n_d()) {
-    ps.diag = ch.diag;
-    ps.d_index = ++ch.nd;
-    if (ch.post_after_d && ch.kc[G] == ch.nd && ch.kc[G] <= n) ps.post = ch.X[ch.kc[G]++];
-  }
-  return ps;
 }
 
 dtc::PassArgs base_args(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start) {
@@ -533,61 +323,6 @@ int launch_reduce_prof(dtc_ctx* ctx, int n_tiles, int n_obs, int batch, double* 
                 8.0 * (double)n_tiles * (n_out < 0 ? n_obs - o_first : n_out) * batch});
   }
   return DTC_OK;
-}
-
-// Shape and matrix family of a pass.
-int pass_shape(const PassSpec& ps) {
-  if (ps.lc_w0 >= 0) return dtc::kShapeLC;
-  const bool has_d = ps.diag != dtc::kDiagNone;
-  if (ps.pre.enabled && has_d && ps.post.enabled) return dtc::kShapeKDK;
-  if (ps.pre.enabled && has_d) return dtc::kShapeKD;
-  if (has_d && ps.post.enabled) return dtc::kShapeDK;
-  if (ps.pre.enabled && !has_d && !ps.post.enabled) return dtc::kShapeK;
-  if (has_d) return dtc::kShapeD;
-  return -1;
-}
-
-int pass_kind(const RunCfg& rc, const PassSpec& ps, int shape) {
-  int kind = shape == dtc::kShapeD ? dtc::kKindRX : -1;
-  std::vector<const KickDesc*> ks{&ps.pre, &ps.post};
-  for (int l = 0; l < ps.lc_layers; ++l)
-    if (lc_layer_bits(ps, l)) ks.push_back(&ps.lc[l]);
-  for (const KickDesc* k : ks) {
-    if (!k->enabled) continue;
-    const bool basis_x = k->mode == dtc::kKickBasisX || k->mode == dtc::kKickUndoBasisX;
-    int rk = basis_x ? dtc::kKindGen : rc.row_kind[k->row];
-    // device-like noise: Kraus x Pauli x gate is not unitary; with one
-    // sub-gate per kick it is a real diagonal times a unitary of the family
-    // (SiteMat in dtc_kernels.hip: factored, the diagonal deferred); Kraus
-    // factors between sub-gates, or a dagger (undo) putting the diagonal on
-    // the right, leave only the general form
-    if (rc.device && (rk == dtc::kKindRX || rk == dtc::kKindRY)) {
-      const bool left_diag = rc.prob->n_sub == 1 && k->mode != dtc::kKickUndo &&
-                             k->mode != dtc::kKickUndoBasisX;
-      rk = !left_diag ? dtc::kKindGen : (rk == dtc::kKindRX ? dtc::kKindRXU : dtc::kKindRYU);
-    }
-    kind = (kind < 0 || kind == rk) ? rk : dtc::kKindGen;
-  }
-  return kind;
-}
-
-dtc::PassKick pass_kick(const RunCfg& rc, const PassSpec& ps) {
-  const Group g = pass_group(rc.pl, ps);
-  dtc::PassKick pk{};
-  pk.pre = ps.pre;
-  pk.post = ps.post;
-  pk.lc_layers = ps.lc_layers;
-  for (int l = 0; l < dtc::kLcMaxLayers; ++l) pk.lc[l] = ps.lc[l];
-  pk.lc_mask = ps.lc_mask;
-  pk.lc_mask2 = ps.lc_mask2;
-  pk.lc_wide = ps.lc_wide;
-  for (int k = 0; k < dtc::kTileBits; ++k) pk.lc_gb[k] = ps.lc_gb[k];
-  pk.kind = pass_kind(rc, ps, pass_shape(ps));
-  pk.c = g.c;
-  pk.s = g.s;
-  pk.act = g.act;
-  pk.tb = g.tb;
-  return pk;
 }
 
 // Launch one pass whose kick records are `recs` ([batch][kRecPerState]; null:
@@ -736,82 +471,6 @@ int launch_pass_spec(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int ba
   return DTC_OK;
 }
 
-// A scheduled pass of a batch (dtc_autocorr builds the whole batch schedule,
-// prepares every kick record with one prep launch per segment, then streams
-// the passes).
-struct Launch {
-  PassSpec ps;
-  const double2* src;
-  double2* dst;
-  int meas_mode, meas_at_end, n_obs;
-  double* meas_out;
-  int64_t meas_stride;
-  int no_store = 0;  // the pass's output is never read again (last pass of an echo chain)
-  const int64_t* basis = nullptr;  // first pass of a sweep: src = the basis states (synthesised)
-  // dual pass (dtc_kdk_dual): ps is a forward K-D-K that also starts an echo
-  // chain -- ps2 = {ps's pre-kick, the echo's first kick layer as post}, its
-  // tile after the pre-kick, kicked by ps2's post, goes to dst2
-  double2* dst2 = nullptr;
-  PassSpec ps2{};
-  // bond noise: the pass's diagonal is the noisy layer drawn at (bond_stream,
-  // bond_counter), of a forward (0) or an inverse (1) period
-  int bond_diag = 0;
-  uint32_t bond_stream = 0, bond_counter = 0;
-  int bond_inv = 0;
-  // wavefront pass (dtc_wavefront.hip): wf_steps > 0 kick steps of layers
-  // wf_kick[st] on the tile bits wf_mask[st] of tile wf_tile (0: index bits
-  // 0..11; 1: three column bits + sites 11..19), partial diagonals per wf_dmask
-  // from table set wf_set, kick family wf_kind; ps is unused
-  int wf_steps = 0, wf_tile = 0, wf_dmask = 0, wf_set = 0, wf_kind = 0;
-  uint32_t wf_mask[dtc::kWfSteps] = {};
-  KickDesc wf_kick[dtc::kWfSteps] = {};
-  // an end of an energy echo chain (dtc_energy_echo; meas_mode kMeasEnergy,
-  // n_obs = 3 L): kPartXEnd -- X of the pass's sites after its last kick,
-  // accumulated into the row at energy_row + 2 L -- and, on the chain's last
-  // pass, kPartZ at the end of the pass into the row's first 2 L values
-  int meas_parts = 0;
-  double* energy_row = nullptr;
-};
-
-// The tile geometry of the wavefront tiles (WfArgs / PassKick c, s, act) and
-// the index bit outside the tile that one of its bonds reaches.
-struct WfGeo {
-  int c, s, act, out_bit, site0;  // site0: the site of tile bit c
-};
-constexpr WfGeo kWfGeo[2] = {{dtc::kTileBits, dtc::kTileBits, 0xFFF, 12, 0}, {3, 11, 0xFF8, 10, 11}};
-constexpr int kWfSetStride = (dtc::kWfSteps + 1) * 2 * dtc::kWfTab;  // double2 per instance
-
-// The two standard record rows of a wavefront launch: row j holds steps 2 j
-// (pre) and 2 j + 1 (post), each cut to its step's tile bits.
-dtc::PassKick wf_pass_kick(const Launch& l, int j) {
-  const WfGeo& g = kWfGeo[l.wf_tile];
-  dtc::PassKick pk{};
-  // (every step's layer in lc[], and the launch's program: the Pauli frame of
-  // the launch runs across both rows, dtc_wf_frame.h)
-  for (int st = 0; st < dtc::kWfSteps; ++st) {
-    KickDesc k = no_kick();
-    if (st < l.wf_steps && l.wf_mask[st]) {
-      k = l.wf_kick[st];
-      k.enabled = 1;
-      k.skip = (uint32_t)g.act & ~l.wf_mask[st];
-    }
-    pk.lc[st] = k;
-    pk.wf_mask[st] = st < l.wf_steps ? l.wf_mask[st] : 0u;
-  }
-  pk.pre = pk.lc[2 * j];
-  pk.post = pk.lc[2 * j + 1];
-  pk.wf_row = 1 + j;
-  pk.wf_steps = l.wf_steps;
-  pk.wf_dmask = l.wf_dmask;
-  pk.kind = l.wf_kind;
-  // (tile bit k < 12 = site k for the low tile: c = 12 serves the records too)
-  pk.c = g.c;
-  pk.s = g.s;
-  pk.act = g.act;
-  pk.tb = dtc::kTileBits;
-  return pk;
-}
-
 int launch_wf(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch, const Launch& l,
               const dtc::KickRec* recs) {
   const WfGeo& g = kWfGeo[l.wf_tile];
@@ -921,17 +580,15 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
                  const std::vector<Launch>& L) {
 #ifdef DTC_DEV_KNOBS
   // development builds: DTC_PRINT_SCHED=1 lists the batch's schedule on stderr
-  if (std::getenv("DTC_PRINT_SCHED")) {
-    auto role = [&](const void* p) {
-      return p == ctx->F.p ? "F" : (p == ctx->E.p ? "E" : (p ? "?" : "-"));
-    };
-    for (size_t i = 0; i < L.size(); ++i)
-      std::fprintf(stderr, "sched %zu g%d shape%d diag%d pre%d post%d lc%d %s->%s%s meas%d%s%s\n", i,
-                   L[i].ps.group, pass_shape(L[i].ps), L[i].ps.diag, L[i].ps.pre.enabled,
-                   L[i].ps.post.enabled, L[i].ps.lc_w0, role(L[i].src), role(L[i].dst),
-                   L[i].dst2 ? "+E" : "", L[i].meas_mode, L[i].no_store ? " nostore" : "",
-                   L[i].basis ? " basis" : "");
-  }
+  // (the listing of tools/schedule_check.cpp; F0 there is the prefix here)
+  if (std::getenv("DTC_PRINT_SCHED"))
+    dump_schedule(stderr, L,
+                  {{"F0", ctx->prefix.p, ctx->prefix.n, 16},
+                   {"F", ctx->F.p, ctx->F.n, 16},
+                   {"E", ctx->E.p, ctx->E.n, 16},
+                   {"vals_f", ctx->vals_f.p, ctx->vals_f.n, 8},
+                   {"vals_e", ctx->vals_e.p, ctx->vals_e.n, 8},
+                   {"basis", ctx->basis.p, ctx->basis.n, 8}});
 #endif
   // one record row per launch, two for a dual pass (its echo branch's kicks)
   std::vector<size_t> row0(L.size() + 1);
@@ -1020,54 +677,6 @@ void batch_layout(const dtc_ctx* ctx, int L_eff, int64_t S, int64_t& B, int& oct
   B = std::min<int64_t>(std::min<int64_t>(B, S), 65535);
   octet = (ctx->octet_bits > 0 && B >= 8 && L_eff <= kOctetMaxLeff) ? ctx->octet_bits : 0;
   if (octet && B < S) B &= ~(int64_t)7;
-}
-
-// Matrix family of each kick-table row: RX if every sub-gate is
-// [[real, imag], [imag, real]], RY if every sub-gate is real, else general.
-// Both families are closed under products, Paulis and daggers.
-std::vector<int> classify_rows(const dtc_problem* pr) {
-  const int n_rows = std::max(1, pr->T - 1 + pr->t_offset);
-  std::vector<int> out(n_rows);
-  const size_t per_row = (size_t)pr->L * pr->n_sub;
-  for (int r = 0; r < n_rows; ++r) {
-    bool rx = true, ry = true;
-    for (size_t e = 0; e < per_row; ++e) {
-      const double* m = pr->kick + ((size_t)r * per_row + e) * 8;
-      // m = {m00.re, m00.im, m01.re, m01.im, m10.re, m10.im, m11.re, m11.im}
-      if (!(m[1] == 0.0 && m[2] == 0.0 && m[4] == 0.0 && m[7] == 0.0)) rx = false;
-      if (!(m[1] == 0.0 && m[3] == 0.0 && m[5] == 0.0 && m[7] == 0.0)) ry = false;
-    }
-    out[r] = rx ? dtc::kKindRX : (ry ? dtc::kKindRY : dtc::kKindGen);
-  }
-  return out;
-}
-
-// Forward chain over periods first .. first + n - 1 (rows period-1, RNG counter
-// = period, stream `stream`), a diagonal after every layer (fast.py:111-121).
-Chain forward_chain(const Plan& pl, int first, int n, uint32_t stream) {
-  Chain ch;
-  for (int k = 0; k < n; ++k)
-    ch.X.push_back(KickDesc{1, first + k - 1, dtc::kKickForward, stream, (uint32_t)(first + k)});
-  ch.trailing_d = true;
-  ch.diag = dtc::kDiagFwd;
-  ch.kc.assign(pl.groups.size(), 0);
-  return ch;
-}
-
-// Echo chain (fast.py:140-143, UF.inverse() per period, periods in reverse):
-// D^* K'_p D^* K'_{p-1} ... D^* K'_1, RNG stream `stream`, counter = step k.
-// `ahead[g]` marks groups whose state already carries the forward layer
-// K_{p+1} (row p): X_0 undoes it exactly before the first D^*.
-Chain echo_chain(const Plan& pl, int p, uint32_t stream, const std::vector<int>& ahead) {
-  Chain ch;
-  ch.X.push_back(KickDesc{1, p, dtc::kKickUndo, dtc::kStreamForward, (uint32_t)(p + 1)});
-  for (int k = 1; k <= p; ++k)
-    ch.X.push_back(KickDesc{1, p - k, dtc::kKickInverse, stream, (uint32_t)k});
-  ch.trailing_d = false;
-  ch.diag = dtc::kDiagConj;
-  ch.kc.resize(pl.groups.size());
-  for (size_t g = 0; g < pl.groups.size(); ++g) ch.kc[g] = ahead[g] ? 0 : 1;
-  return ch;
 }
 
 // Run a whole chain; the first pass reads src, every pass writes dst; the
@@ -1242,7 +851,6 @@ int upload_tables(dtc_ctx* ctx, const dtc_problem* pr, const Plan& pl) {
   return DTC_OK;
 }
 
-
 // ---- sharded state (include/dtc.h: dtc_shard) ---------------------------------
 
 int check_shard(const dtc_problem* pr, const dtc_shard* sh) {
@@ -1296,225 +904,6 @@ void shard_chain(const dtc_problem* pr, const dtc_shard* sh, int inst, int rank,
   *c_angle = c;
 }
 
-uint64_t group_bits(const Group& g) {
-  uint64_t m = 0;
-  for (int k = 0; k < g.tb; ++k)
-    if (g.act & (1 << k)) m |= 1ull << (k < g.c ? k : g.s + k - g.c);
-  return m;
-}
-
-// The kick sites of layer `k` in a pass over group g (tile bits outside
-// k.skip), below L.
-uint64_t layer_sites(const Group& g, const KickDesc& k, int L) {
-  uint64_t m = 0;
-  for (int b = 0; b < g.tb; ++b) {
-    if (!(g.act & ~(int)k.skip & (1 << b))) continue;
-    const int site = b < g.c ? b : g.s + b - g.c;
-    if (site < L) m |= 1ull << site;
-  }
-  return m;
-}
-
-// tile bits of group g that are NOT in mask (left identity by a kick layer)
-uint32_t skip_bits(const Group& g, uint64_t mask) {
-  uint32_t sk = 0;
-  for (int k = 0; k < g.tb; ++k) {
-    if (!(g.act & (1 << k))) continue;
-    const int bit = k < g.c ? k : g.s + k - g.c;
-    if (!((mask >> bit) & 1)) sk |= 1u << k;
-  }
-  return sk;
-}
-
-// The kick layers of a chain's last k passes, in order, separated by the
-// D*'s (a layer of one period spans two passes: the post-kick of one group and
-// the pre-kick of the next); trailing diagonals are dropped.  False when the
-// passes do not form such layers (not a D* chain, a light-cone pass already).
-bool lc_layers_of(const RunCfg& rc, const std::vector<Launch>& sched, int k,
-                  std::vector<KickDesc>& desc, std::vector<uint64_t>& sites) {
-  const Plan& pl = rc.pl;
-  auto same_layer = [](const KickDesc& a, const KickDesc& b) {
-    return a.row == b.row && a.mode == b.mode && a.stream == b.stream &&
-           a.rng_period == b.rng_period;
-  };
-  desc.assign(1, no_kick());
-  sites.assign(1, 0);
-  bool ok = true;
-  int pending_d = 0;  // diagonals not yet followed by a kick (trailing ones are dropped)
-  auto kick = [&](const Group& g, const KickDesc& kd) {
-    for (; pending_d > 0; --pending_d) {
-      desc.push_back(no_kick());
-      sites.push_back(0);
-    }
-    if (desc.back().enabled && !same_layer(desc.back(), kd)) ok = false;
-    desc.back() = kd;
-    desc.back().skip = 0;
-    sites.back() |= layer_sites(g, kd, pl.L);
-  };
-  for (size_t i = sched.size() - k; i < sched.size(); ++i) {
-    const PassSpec& ps = sched[i].ps;
-    if (ps.lc_w0 >= 0) ok = false;
-    if (!ok) break;
-    const Group& g = pl.groups[ps.group];
-    if (ps.pre.enabled) kick(g, ps.pre);
-    if (ps.diag != dtc::kDiagNone) {
-      if (ps.diag != dtc::kDiagConj) ok = false;
-      ++pending_d;
-    }
-    if (ps.post.enabled) kick(g, ps.post);
-  }
-  return ok;
-}
-
-// The sites of j's cone (radius r), clipped to [0, L).
-uint64_t cone_sites(int L, int j, int r) {
-  uint64_t cone = 0;
-  for (int i = std::max(0, j - r); i <= std::min(L - 1, j + r); ++i) cone |= 1ull << i;
-  return cone;
-}
-
-// The 10-site light-cone end (dtc_lcw_final): the chain's last five passes
-// as six layers r = 5 .. 0 on the window j-5 .. j+4 or j-4 .. j+5 (the cone
-// of r = 4 plus the first layer's group), tile bits 0, 1 = global bits 0, 1.
-// The kernel's fixed nibble program needs layers r <= 1 on j-2 .. j+1 (nibble
-// 1), r <= 3 on nibbles 1 and 2 (+ j+2, j+3, j-4, j-3): checked here, as the
-// window's bounds; false leaves the chain to lc_merge's 8-site form.
-bool lc_merge_wide(const RunCfg& rc, std::vector<Launch>& sched, size_t chain0, int j) {
-  const Plan& pl = rc.pl;
-  const int L = pl.L;
-  if ((int)(sched.size() - chain0) < 5) return false;
-  if (j - 4 < 2 || j + 3 > L - 1) return false;
-  std::vector<KickDesc> desc;
-  std::vector<uint64_t> sites;
-  if (!lc_layers_of(rc, sched, 5, desc, sites) || (int)desc.size() != dtc::kLcwLayers) return false;
-  uint64_t u = 1ull << j;
-  for (int l = 0; l < dtc::kLcwLayers; ++l) {
-    sites[l] &= cone_sites(L, j, dtc::kLcwLayers - 1 - l);
-    u |= sites[l];
-  }
-  const uint64_t nib1 = 0xFull << (j - 2);
-  const uint64_t nib2 = (3ull << (j + 2)) | (3ull << (j - 4));
-  if ((sites[4] | sites[5]) & ~nib1) return false;
-  if ((sites[2] | sites[3]) & ~(nib1 | nib2)) return false;
-  uint64_t rest = u & ~(nib1 | nib2);
-  if (__builtin_popcountll(rest) > 2 || (rest & 3ull)) return false;
-  // the two low tile bits beside the columns: the outer sites, padded with
-  // free bits of the state (their kicks stay off)
-  for (int g = 2; g < pl.L_eff && __builtin_popcountll(rest) < 2; ++g)
-    if (!(((nib1 | nib2 | rest) >> g) & 1ull)) rest |= 1ull << g;
-  if (__builtin_popcountll(rest) != 2) return false;
-  PassSpec lc{sched.back().ps.group, no_kick(), no_kick(), dtc::kDiagConj, sched.back().ps.d_index};
-  const int r0 = __builtin_ctzll(rest), r1 = 63 - __builtin_clzll(rest);
-  const int gb[dtc::kTileBits] = {0, 1, r0, r1, j - 2, j - 1, j, j + 1, j + 2, j + 3, j - 4, j - 3};
-  lc.lc_w0 = j - 4;  // (marks the light-cone pass; the tile is lc_gb)
-  lc.lc_wide = 1;
-  lc.lc_layers = dtc::kLcwLayers;
-  for (int k = 0; k < dtc::kTileBits; ++k) lc.lc_gb[k] = (int8_t)gb[k];
-  for (int l = 0; l < dtc::kLcwLayers; ++l) {
-    lc.lc[l] = desc[l];
-    for (int k = 2; k < dtc::kTileBits; ++k)
-      if ((sites[l] >> gb[k]) & 1ull) lc.lc_mask |= 1ull << (10 * l + k - 2);
-  }
-  const int kind = pass_kind(rc, lc, dtc::kShapeLC);
-  if (kind != dtc::kKindRX && kind != dtc::kKindRY) return false;
-  const Launch first = sched[sched.size() - 5];
-  sched.resize(sched.size() - 5 + 1);
-  sched.back() = Launch{lc, first.src, first.dst, dtc::kMeasProbe, 1, 2, nullptr, first.meas_stride};
-  return true;
-}
-
-// The 12-site light-cone end (dtc_lcw3_final): the chain's last six passes
-// as seven layers r = 6 .. 0 on the window j-5 .. j+6, tile bit k = global
-// bit j-5+k (no column bits).  The kernel runs a fixed program: layer l may
-// kick only sites of its cone that the program visits (l0: j+2 .. j+6 -- the
-// C2 chains' first layer is group B's pre-kick; l1: j-5 .. j+5; then the
-// cones of radius 4 .. 0); a site the chain leaves unkicked gets the identity
-// record.  False leaves the chain to lc_merge_wide.
-bool lc_merge_wide7(const RunCfg& rc, std::vector<Launch>& sched, size_t chain0, int j) {
-  const Plan& pl = rc.pl;
-  const int L = pl.L;
-  if ((int)(sched.size() - chain0) < 6) return false;
-  if (j - 6 < 0 || j + 6 > L - 1 || pl.L_eff != L || pl.L_eff > 32) return false;
-  std::vector<KickDesc> desc;
-  std::vector<uint64_t> sites;
-  if (!lc_layers_of(rc, sched, 6, desc, sites) || (int)desc.size() != dtc::kLcw3Layers) return false;
-  auto span = [&](int a, int b) {  // sites j+a .. j+b
-    uint64_t m = 0;
-    for (int i = j + a; i <= j + b; ++i) m |= 1ull << i;
-    return m;
-  };
-  const uint64_t prog[dtc::kLcw3Layers] = {span(2, 6), span(-5, 5), span(-4, 4), span(-3, 3),
-                                           span(-2, 2), span(-1, 1), span(0, 0)};
-  for (int l = 0; l < dtc::kLcw3Layers; ++l) {
-    sites[l] &= cone_sites(L, j, dtc::kLcw3Layers - 1 - l);
-    if (sites[l] & ~prog[l]) return false;
-  }
-  PassSpec lc{sched.back().ps.group, no_kick(), no_kick(), dtc::kDiagConj, sched.back().ps.d_index};
-  lc.lc_w0 = j - 5;  // (marks the light-cone pass; the tile is lc_gb)
-  lc.lc_wide = 2;
-  lc.lc_layers = dtc::kLcw3Layers;
-  for (int k = 0; k < dtc::kTileBits; ++k) lc.lc_gb[k] = (int8_t)(j - 5 + k);
-  for (int l = 0; l < dtc::kLcw3Layers; ++l) {
-    lc.lc[l] = desc[l];
-    for (int k = 0; k < dtc::kTileBits; ++k)
-      if ((sites[l] >> (j - 5 + k)) & 1ull) {
-        const int bit = 12 * l + k;
-        if (bit < 64) lc.lc_mask |= 1ull << bit;
-        else lc.lc_mask2 |= 1ull << (bit - 64);
-      }
-  }
-  const int kind = pass_kind(rc, lc, dtc::kShapeLC);
-  if (kind != dtc::kKindRX && kind != dtc::kKindRY) return false;
-  const Launch first = sched[sched.size() - 6];
-  sched.resize(sched.size() - 6 + 1);
-  sched.back() = Launch{lc, first.src, first.dst, dtc::kMeasProbe, 1, 2, nullptr, first.meas_stride};
-  return true;
-}
-
-// Light-cone end of the echo chain sched[chain0 ..) measuring Z_j: replace
-// its last k passes by one kShapeLC pass -- six (lc_merge_wide7) or five
-// (lc_merge_wide), when enabled and they fit, else k = 4 .. 2 (the first that
-// fits) over an 8-site window.
-// Layer l of M (r = M - 1 - l diagonals before the probe) only matters on
-// sites j-r .. j+r, and the layers' remaining sites must fit the window
-// w0 .. w0+7 (4 <= w0 <= L - 8: clear of tile bits 0..3).
-void lc_merge(const RunCfg& rc, std::vector<Launch>& sched, size_t chain0, int j, bool wide,
-              bool wide3) {
-  const Plan& pl = rc.pl;
-  const int L = pl.L;
-  if (wide3 && lc_merge_wide7(rc, sched, chain0, j)) return;
-  if (wide && lc_merge_wide(rc, sched, chain0, j)) return;
-  const int n_chain = (int)(sched.size() - chain0);
-  for (int k = std::min(4, n_chain); k >= 2; --k) {
-    std::vector<KickDesc> desc;
-    std::vector<uint64_t> sites;
-    const bool ok = lc_layers_of(rc, sched, k, desc, sites);
-    const int M = (int)desc.size();
-    if (!ok || M > dtc::kLcLayers) continue;
-    uint64_t u = 1ull << j;
-    for (int l = 0; l < M; ++l) {
-      sites[l] &= cone_sites(L, j, M - 1 - l);
-      u |= sites[l];
-    }
-    const int lo = __builtin_ctzll(u), hi = 63 - __builtin_clzll(u);
-    const int w0 = std::max(4, std::min(lo, L - 8));
-    if (w0 > lo || hi > w0 + 7 || w0 + 8 > pl.L_eff) continue;
-    const PassSpec& last = sched.back().ps;
-    PassSpec lc{last.group, no_kick(), no_kick(), dtc::kDiagConj, last.d_index};
-    lc.lc_w0 = w0;
-    lc.lc_layers = M;
-    for (int l = 0; l < M; ++l) {
-      lc.lc[l] = desc[l];
-      lc.lc_mask |= ((sites[l] >> w0) & 0xFFull) << (dtc::kLcSites * l);
-    }
-    const int kind = pass_kind(rc, lc, dtc::kShapeLC);
-    if (kind != dtc::kKindRX && kind != dtc::kKindRY) continue;
-    const Launch first = sched[sched.size() - k];
-    sched.resize(sched.size() - k + 1);
-    sched.back() = Launch{lc, first.src, first.dst, dtc::kMeasProbe, 1, 2, nullptr, first.meas_stride};
-    return;
-  }
-}
 }  // namespace
 
 extern "C" {
@@ -1551,17 +940,17 @@ int dtc_open(int32_t device, dtc_ctx** out) {
 #endif
   // documented test switches (the parity tests compare the light-cone ends
   // with the full passes, each form on its own engine)
-  c->lightcone = std::getenv("DTC_NO_LIGHTCONE") == nullptr;
-  c->lc_wide = std::getenv("DTC_NO_LCW") == nullptr;
-  c->lc_wide3 = c->lc_wide && std::getenv("DTC_NO_LCW3") == nullptr;
-  c->dual = std::getenv("DTC_NO_DUAL") == nullptr;
+  c->so.lightcone = std::getenv("DTC_NO_LIGHTCONE") == nullptr;
+  c->so.lc_wide = std::getenv("DTC_NO_LCW") == nullptr;
+  c->so.lc_wide3 = c->so.lc_wide && std::getenv("DTC_NO_LCW3") == nullptr;
+  c->so.dual = std::getenv("DTC_NO_DUAL") == nullptr;
   if (const char* e = std::getenv("DTC_WAVEFRONT")) {
     const int v = std::atoi(e);
-    if (v >= 2 && v <= dtc::kWfSteps) c->wf_cap = v;
+    if (v >= 2 && v <= dtc::kWfSteps) c->so.wf_cap = v;
   }
-  if (std::getenv("DTC_NO_WAVEFRONT")) c->wavefront = false;
-  c->runahead = std::getenv("DTC_NO_RUNAHEAD") == nullptr;
-  if (const char* e = std::getenv("DTC_SPLIT13")) c->split13 = std::atoi(e) != 0;
+  if (std::getenv("DTC_NO_WAVEFRONT")) c->so.wavefront = false;
+  c->so.runahead = std::getenv("DTC_NO_RUNAHEAD") == nullptr;
+  if (const char* e = std::getenv("DTC_SPLIT13")) c->so.split13 = std::atoi(e) != 0;
   c->verbose = std::getenv("DTC_VERBOSE") != nullptr;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
     delete c;
@@ -1830,197 +1219,6 @@ uint64_t prefix_hash(const dtc_problem* pr, int n_periods) {
   return h;
 }
 
-// ---- wavefront interior of an echo chain ------------------------------------
-// The partial-diagonal table sets of a sweep, one per distinct (tile, factor
-// sets of the steps): [set][n_inst][step][outside bit][kWfTab] (WfArgs::tab),
-// built on the host as the schedule meets them.
-struct WfTables {
-  std::vector<std::string> keys;
-  std::vector<double> host;  // re, im pairs
-  bool dirty = false;
-};
-
-// The table set of one planned pass (conjugated factors: the echo's D^*).
-int wf_table_set(const dtc_problem* pr, const dtc::wf::Pass& ps, bool conj, WfTables& wt) {
-  const WfGeo& g = kWfGeo[ps.tile];
-  const int L = pr->L;
-  std::string key(1, (char)('0' + ps.tile));
-  key += conj ? 'c' : 'f';
-  for (const dtc::wf::Step& sp : ps.steps) {
-    key += sp.kick_mask ? '|' : '/';
-    for (const dtc::wf::Factor& f : sp.factors) {
-      key += f.bond ? 'b' : 'f';
-      key += (char)('A' + f.site);
-    }
-  }
-  for (size_t i = 0; i < wt.keys.size(); ++i)
-    if (wt.keys[i] == key) return (int)i;
-  const int set = (int)wt.keys.size();
-  wt.keys.push_back(key);
-  wt.dirty = true;
-  const size_t per_set = (size_t)pr->n_inst * kWfSetStride * 2;
-  wt.host.resize((size_t)(set + 1) * per_set);
-  double* base = wt.host.data() + (size_t)set * per_set;
-  for (size_t e = 0; e < per_set; e += 2) {
-    base[e] = 1.0;
-    base[e + 1] = 0.0;
-  }
-  auto tile_bit = [&](int site) { return site - g.site0 + (g.c == dtc::kTileBits ? 0 : g.c); };
-  auto in_tile = [&](int site) { return site >= g.site0 && tile_bit(site) < dtc::kTileBits; };
-  const double sgn = conj ? 0.5 : -0.5;
-  // kick steps first, then the trailing kick-less one: table slot st
-  int st = 0;
-  for (const dtc::wf::Step& sp : ps.steps) {
-    const int slot = sp.kick_mask ? st++ : st;
-    if (sp.factors.empty()) continue;
-    for (int in = 0; in < pr->n_inst; ++in) {
-      const double* hh = pr->h + (size_t)in * L;
-      const double* pp = pr->phi + (size_t)in * (L - 1);
-      for (int var = 0; var < 2; ++var) {
-        double* o = base + (((size_t)in * (dtc::kWfSteps + 1) + slot) * 2 + var) * dtc::kWfTab * 2;
-        const double zout = var ? -1.0 : 1.0;
-        if (dtc::kWfT2Lay1 && g.c == 3 && (slot & 1)) {
-          // the column tile's odd slots: its diagonal runs in layout 1, the same
-          // factors regrouped into the register table (half 0, over tile bits
-          // 3..8) and the thread table (half 1, bits 3, 8..11), dtc_wf_frame.h
-          for (int half = 0; half < 2; ++half) {
-            const int n_ent = half ? dtc::kWfL1Thr : dtc::kWfL1Reg;
-            for (int v = 0; v < n_ent; ++v) {
-              auto z = [&](int k) {
-                const int pos = half ? dtc::wf_l1_thr_pos(k) : dtc::wf_l1_reg_pos(k);
-                return (pos >= 0 && ((v >> pos) & 1)) ? -1.0 : 1.0;
-              };
-              double ang = 0.0;
-              for (const dtc::wf::Factor& f : sp.factors) {
-                if (!f.bond) {
-                  const int k = tile_bit(f.site);
-                  if (dtc::wf_l1_in_reg(k, -1) == (half == 0)) ang += hh[f.site] * z(k);
-                } else if (in_tile(f.site) && in_tile(f.site + 1)) {
-                  const int k = tile_bit(f.site);
-                  if (dtc::wf_l1_in_reg(k, k + 1) == (half == 0)) ang += pp[f.site] * z(k) * z(k + 1);
-                } else {
-                  const int k = tile_bit(in_tile(f.site) ? f.site : f.site + 1);
-                  if (dtc::wf_l1_in_reg(k, -1) == (half == 0)) ang += pp[f.site] * z(k) * zout;
-                }
-              }
-              double* e = o + ((size_t)(half ? dtc::kWfL1Reg : 0) + v) * 2;
-              e[0] = std::cos(sgn * ang);
-              e[1] = std::sin(sgn * ang);
-            }
-          }
-          continue;
-        }
-        for (int half = 0; half < 2; ++half) {
-          // half 0: index = tile bits 0..6; half 1: tile bits 6..11
-          const int bit0 = half ? 6 : 0, n_ent = half ? dtc::kWfTabB : dtc::kWfTabA;
-          for (int v = 0; v < n_ent; ++v) {
-            auto z = [&](int k) { return ((v >> (k - bit0)) & 1) ? -1.0 : 1.0; };
-            double ang = 0.0;
-            for (const dtc::wf::Factor& f : sp.factors) {
-              if (!f.bond) {
-                const int k = tile_bit(f.site);
-                if ((k <= 5) == (half == 0)) ang += hh[f.site] * z(k);
-              } else if (in_tile(f.site) && in_tile(f.site + 1)) {
-                const int k = tile_bit(f.site);
-                if ((k <= 5) == (half == 0)) ang += pp[f.site] * z(k) * z(k + 1);
-              } else {
-                const int k = tile_bit(in_tile(f.site) ? f.site : f.site + 1);
-                if ((k <= 5) == (half == 0)) ang += pp[f.site] * z(k) * zout;
-              }
-            }
-            double* e = o + ((size_t)(half ? dtc::kWfTabA : 0) + v) * 2;
-            e[0] = std::cos(sgn * ang);
-            e[1] = std::sin(sgn * ang);
-          }
-        }
-      }
-    }
-  }
-  return set;
-}
-
-// Replace the run of plain stored K-D-K launches sched[r0, r1) of an echo
-// chain -- alternating between the two site groups, launch i applying layer i
-// as its pre-kick, D^*, layer i + 1 as its post-kick -- by the planner's
-// passes over the overlapping tiles.  Leaves the schedule alone (returns
-// false) when anything about the run is not the plain pattern.
-bool wf_replace(dtc_ctx* ctx, const RunCfg& rc, std::vector<Launch>& sched, size_t r0, size_t r1,
-                WfTables& wt) {
-  const int n = (int)(r1 - r0);
-  if (n < 3) return false;
-  auto same_layer = [](const KickDesc& a, const KickDesc& b) {
-    return a.row == b.row && a.mode == b.mode && a.stream == b.stream &&
-           a.rng_period == b.rng_period;
-  };
-  std::vector<KickDesc> layer(n + 1);
-  int kind = -1;
-  for (int i = 0; i < n; ++i) {
-    const Launch& l = sched[r0 + i];
-    const PassSpec& ps = l.ps;
-    if (pass_shape(ps) != dtc::kShapeKDK || ps.lc_w0 >= 0 || ps.diag != dtc::kDiagConj ||
-        ps.pre.mode != dtc::kKickInverse || ps.post.mode != dtc::kKickInverse || ps.pre.skip ||
-        ps.post.skip || ps.pre.bond_on || ps.post.bond_on || l.meas_mode != dtc::kMeasNone ||
-        l.no_store || l.basis || l.dst2 || l.bond_diag || l.wf_steps || l.src != l.dst ||
-        ps.group != (sched[r0].ps.group ^ (i & 1)))
-      return false;
-    if (i > 0 && !same_layer(sched[r0 + i - 1].ps.post, ps.pre)) return false;
-    layer[i] = ps.pre;
-    layer[i + 1] = ps.post;
-  }
-  for (const KickDesc& k : layer) {
-    const int rk = rc.row_kind[k.row];
-    if (rk != dtc::kKindRX && rk != dtc::kKindRY) return false;
-    if (kind >= 0 && rk != kind) return false;  // one kick family per pass
-    kind = rk;
-  }
-  // planner layers 1 .. n + 1 = layer[0 .. n]; the first launch's group is the
-  // one behind at entry
-  dtc::wf::Problem p = dtc::wf::plain_span(20, 12, 1, sched[r0].ps.group != 0, n);
-  p.tiles = {dtc::wf::make_tile(0, 0, 12), dtc::wf::make_tile(3, 11, 9)};
-  p.cap = ctx->wf_cap;
-  std::vector<dtc::wf::Pass> plan;
-  // a plan must save launches -- except at cap 2 (DTC_WAVEFRONT=2), which lifts
-  // a tile's sites by two layers per pass, the plain rate, and never can: that
-  // setting only ever is the test switch for the two-step passes, so there a
-  // plan of the plain length runs
-  if (!dtc::wf::plan(p, plan) || (int)plan.size() > n ||
-      ((int)plan.size() == n && ctx->wf_cap != 2))
-    return false;
-  std::vector<Launch> out;
-  for (const dtc::wf::Pass& ps : plan) {
-    Launch l = sched[r0];
-    l.ps = PassSpec{ps.tile, no_kick(), no_kick(), dtc::kDiagConj, 0};
-    l.wf_tile = ps.tile;
-    l.wf_kind = kind;
-    l.wf_steps = 0;
-    l.wf_dmask = 0;
-    for (const dtc::wf::Step& sp : ps.steps) {
-      if (!sp.kick_mask) {
-        l.wf_dmask |= 1 << l.wf_steps;  // the trailing step
-        continue;
-      }
-      if (l.wf_steps >= dtc::kWfSteps) return false;
-      int m = -1;
-      for (int k = 0; k < dtc::kTileBits; ++k) {
-        if (!((sp.kick_mask >> k) & 1u)) continue;
-        if (m >= 0 && sp.layer[k] != m) return false;  // one layer per step (the kernel's records)
-        m = sp.layer[k];
-      }
-      if (m < 1 || m > n + 1) return false;
-      if (!sp.factors.empty()) l.wf_dmask |= 1 << l.wf_steps;
-      l.wf_mask[l.wf_steps] = sp.kick_mask;
-      l.wf_kick[l.wf_steps] = layer[m - 1];
-      ++l.wf_steps;
-    }
-    if (l.wf_steps < 1) return false;  // (a kick-less pass: not planned for these spans)
-    l.wf_set = wf_table_set(rc.prob, ps, true, wt);
-    out.push_back(l);
-  }
-  sched.erase(sched.begin() + (std::ptrdiff_t)r0, sched.begin() + (std::ptrdiff_t)r1);
-  sched.insert(sched.begin() + (std::ptrdiff_t)r0, out.begin(), out.end());
-  return true;
-}
-
 // The outputs of dtc_energy_echo / dtc_energy_echo_sums (shapes of dtc_energy /
 // dtc_energy_sums): with them autocorr_impl runs its echo sweep with the
 // forward unmeasured and every chain ending in the energy measurements.
@@ -2029,10 +1227,216 @@ struct EchoEnergyOut {
   bool sums;
 };
 
+// A batch's finished rows hv[nb][T][3 L] (norm, Z_i | Z_i Z_i+1 | X_i per time)
+// into the caller's per-trajectory arrays; the row of the initial time is
+// formed from the state's mask.  Rows before t_first (dtc_energy_echo: their
+// chains are not built) are left 0.
 void energy_rows_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
-                     int nb, int t_first, double* z, double* zz, double* x);
+                     int nb, int t_first, double* z, double* zz, double* x) {
+  const int T = pr->T, L = pr->L, n_v = 3 * L;
+  for (int b = 0; b < nb; ++b) {
+    const int64_t g = bs + b;
+    const uint64_t m = (uint64_t)masks[b];
+    for (int t = 0; t < T; ++t) {
+      const bool at_init = (t + pr->t_offset == 0), skip = t < t_first;
+      const double* vf = hv + ((size_t)b * T + t) * n_v;
+      const double* vx = vf + 2 * L - 1;  // X_i at vx[1 + i]
+      double* zo = z + ((size_t)g * T + t) * L;
+      double* xo = x + ((size_t)g * T + t) * L;
+      for (int i = 0; i < L; ++i) {
+        zo[i] = skip ? 0.0 : (at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0) : vf[1 + i]);
+        xo[i] = (skip || at_init) ? 0.0 : vx[1 + i];
+      }
+      if (L > 1) {
+        double* zzo = zz + ((size_t)g * T + t) * (L - 1);
+        for (int i = 0; i + 1 < L; ++i)
+          zzo[i] = skip ? 0.0
+                        : (at_init ? ((((m >> i) ^ (m >> (i + 1))) & 1ull) ? -1.0 : 1.0)
+                                   : vf[1 + L + i]);
+      }
+    }
+  }
+}
+
+// The same for the per-instance sums of a batch's rows (traj_sum_kernel),
+// hv[instances of the batch][T][3 L], added to the caller's zeroed sums.
 void energy_sums_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
-                     int nb, int n_traj, int t_first, double* z, double* zz, double* x);
+                     int nb, int n_traj, int t_first, double* z, double* zz, double* x) {
+  const int T = pr->T, L = pr->L, n_v = 3 * L;
+  const int64_t i0 = bs / n_traj, n_ib = (bs + nb - 1) / n_traj - i0 + 1;
+  for (int64_t i = 0; i < n_ib; ++i) {
+    const int64_t inst = i0 + i;
+    for (int t = t_first; t < T; ++t) {
+      if (t + pr->t_offset == 0) continue;
+      const double* vf = hv + ((size_t)i * T + t) * n_v;
+      const double* vx = vf + 2 * L - 1;
+      double* zo = z + ((size_t)inst * T + t) * L;
+      double* xo = x + ((size_t)inst * T + t) * L;
+      for (int k = 0; k < L; ++k) {
+        zo[k] += vf[1 + k];
+        xo[k] += vx[1 + k];
+      }
+      if (L > 1) {
+        double* zzo = zz + ((size_t)inst * T + t) * (L - 1);
+        for (int k = 0; k + 1 < L; ++k) zzo[k] += vf[1 + L + k];
+      }
+    }
+  }
+  if (pr->t_offset == 0 && t_first == 0) {
+    for (int b = 0; b < nb; ++b) {
+      const int64_t inst = (bs + b) / n_traj;
+      const uint64_t m = (uint64_t)masks[b];
+      double* zo = z + (size_t)inst * T * L;
+      for (int k = 0; k < L; ++k) zo[k] += ((m >> k) & 1ull) ? -1.0 : 1.0;
+      if (L > 1) {
+        double* zzo = zz + (size_t)inst * T * (L - 1);
+        for (int k = 0; k + 1 < L; ++k)
+          zzo[k] += (((m >> k) ^ (m >> (k + 1))) & 1ull) ? -1.0 : 1.0;
+      }
+    }
+  }
+}
+
+// The run configuration of a batched entry point (autocorr, prefix, energy):
+// the trajectory checks, the device, the kick rows' families, the plan, the
+// depolarizing thresholds, the tables of device-like and bond noise.  plain13:
+// the call may run the 13 / 7 split (autocorr_plan, dtc_schedule.h).
+int init_run_cfg(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                 const dtc_device_noise* dv, const dtc_bond_noise* bond, uint64_t seed,
+                 int64_t traj_offset, int32_t n_traj, bool plain13, RunCfg& rc) {
+  if (n_traj < 1) return fail(DTC_EINVAL, "n_traj must be >= 1");
+  if (traj_offset < 0) return fail(DTC_EINVAL, "traj_offset must be >= 0");
+  DTC_HIP(hipSetDevice(ctx->device));
+  rc.prob = pr;
+  rc.seed = seed;
+  rc.traj_offset = traj_offset;
+  rc.n_traj = n_traj;
+  rc.noisy = nz->p > 0.0 ? 1 : 0;
+  rc.row_kind = classify_rows(pr);
+  rc.pl = autocorr_plan(pr->L, rc.row_kind, ctx->so, plain13);
+  thresholds(nz->p, &rc.thr1, &rc.thr2, &rc.thr3);
+  if (dv) DTC_TRY(setup_device_noise(ctx, pr, dv, rc));
+  if (bond) DTC_TRY(setup_bond_noise(ctx, pr, bond, rc));
+  return DTC_OK;
+}
+
+// Automatic batch size: states of per_state bytes within a share of the free
+// memory plus `reusable` (the batch buffers this call may reuse or regrow).
+// Small states: ~64 GiB of batch saturates the device; with large_state_rule
+// (the autocorrelator), large states (L >= 24, C4-style instance batches) may
+// use most of the 288 GB, and DTC_BATCH_BYTES (development builds) sets the
+// budget.
+int auto_batch(dtc_ctx* ctx, double per_state, size_t reusable, bool large_state_rule,
+               int64_t& B) {
+  size_t free_b = 0, total_b = 0;
+  DTC_HIP(hipMemGetInfo(&free_b, &total_b));
+  free_b += reusable;
+  double budget = (large_state_rule && per_state >= (double)(256ull << 20))
+                      ? 0.7 * (double)free_b
+                      : std::min(0.6 * (double)free_b, 64.0 * (1ull << 30));
+  if (large_state_rule && ctx->batch_bytes > 0) budget = ctx->batch_bytes;
+  B = (int64_t)(budget / per_state);
+  B = std::max<int64_t>(1, std::min<int64_t>(B, 4096));
+  return DTC_OK;
+}
+
+// What a prefixed run needs of the prefix in place (dtc_prefix_build).
+int check_prefix(const dtc_ctx* ctx, const dtc_problem* pr, const RunCfg& rc, int64_t S,
+                 bool device) {
+  const int n_pre = ctx->prefix_periods;
+  if (n_pre < 0) return fail(DTC_EINVAL, "no prefix built");
+  if (ctx->prefix_states != S || ctx->prefix_n_traj != rc.n_traj ||
+      ctx->prefix_traj_offset != rc.traj_offset || ctx->prefix_len != rc.pl.len ||
+      ctx->prefix_device != (device ? 1 : 0))
+    return fail(DTC_EINVAL, "prefix built for other trajectories / size / noise kind");
+  if (pr->t_first + pr->t_offset <= n_pre || pr->T - 1 + pr->t_offset <= n_pre)
+    return fail(DTC_EINVAL, "prefixed run must measure only after the prefix's periods");
+  if (prefix_hash(pr, n_pre) != ctx->prefix_hash)
+    return fail(DTC_EINVAL, "problem differs from the prefix's in angles or kick rows");
+  return DTC_OK;
+}
+
+// A batch's finished autocorrelator rows -- hv_f[nb][T][n_obs_f] (the probe, or
+// per-site Z when zsite) and hv_e[nb][T][2] -- into the caller's arrays (each
+// nullable: not wanted).  fac: the ancilla gates' factor; read-out:
+// measured = ro_a * a + ro_b (identity without device noise).
+struct ReadOut {
+  double fac, ro_a, ro_b;
+};
+void autocorr_rows_out(const RunCfg& rc, const ReadOut& ro, const double* hv_f, const double* hv_e,
+                       const int64_t* masks, int64_t bs, int nb, double* fwd, double* echo,
+                       double* zsite) {
+  const dtc_problem* pr = rc.prob;
+  const int T = pr->T, L = pr->L, j = pr->probe_site;
+  const bool want_z = zsite != nullptr;
+  const int n_obs_f = want_z ? 1 + L : 2;
+  for (int b = 0; b < nb; ++b) {
+    const int64_t g = bs + b;
+    const uint64_t m = (uint64_t)masks[b];
+    const double zinit = ((m >> j) & 1ull) ? -1.0 : 1.0;
+    for (int t = std::max(0, pr->t_first); t < T; ++t) {
+      const bool at_init = (t + pr->t_offset == 0);
+      const double* vf = hv_f + ((size_t)b * T + t) * n_obs_f;
+      // bond noise: the forward state at t is measured before its layer's
+      // outgoing Pauli P_t, whose X content flips the sign of <Z_i>
+      const uint64_t px =
+          (rc.bond && !at_init)
+              ? bond_out_x(rc, (uint64_t)(rc.traj_offset + g % rc.n_traj), dtc::kStreamForward,
+                           (uint32_t)(t + pr->t_offset))
+              : 0ull;
+      const double zj_f = (at_init ? zinit : (want_z ? vf[1 + j] : vf[1])) *
+                          (((px >> j) & 1ull) ? -1.0 : 1.0);
+      if (fwd) fwd[(size_t)g * T + t] = ro.ro_a * (ro.fac * zinit * zj_f) + ro.ro_b;
+      if (want_z) {
+        double* zo = zsite + ((size_t)g * T + t) * L;
+        for (int i = 0; i < L; ++i)
+          zo[i] = at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0)
+                          : (((px >> i) & 1ull) ? -vf[1 + i] : vf[1 + i]);
+      }
+      if (echo) {
+        const double zj_e = at_init ? zinit : hv_e[((size_t)b * T + t) * 2 + 1];
+        echo[(size_t)g * T + t] = ro.ro_a * (ro.fac * zinit * zj_e) + ro.ro_b;
+      }
+    }
+  }
+}
+
+// The new wavefront table sets of a schedule (the first batch's), uploaded
+// while the stream is idle.
+int upload_wf_tables(dtc_ctx* ctx, WfTables& wt) {
+  if (!wt.dirty) return DTC_OK;
+  DTC_HIP(hipStreamSynchronize(ctx->stream));
+  DTC_TRY(ensure(ctx->wf_tab, wt.host.size() * sizeof(double)));
+  DTC_HIP(hipMemcpy(ctx->wf_tab.p, wt.host.data(), wt.host.size() * sizeof(double),
+                    hipMemcpyHostToDevice));
+  wt.dirty = false;
+  return DTC_OK;
+}
+
+// The energy echo's finished batch (vals_e[nb][T][3 L]) into the caller's arrays
+// through the staging hv_e: the rows, or their per-instance sums
+// (traj_sum_kernel into vals_f, as dtc_energy_sums).
+int energy_echo_out(dtc_ctx* ctx, const dtc_problem* pr, const EchoEnergyOut& ee,
+                    const int64_t* masks, int64_t bs, int nb, int n_traj, double* hv_e) {
+  const size_t vs = (size_t)pr->T * 3 * pr->L;
+  size_t n_rows = (size_t)nb;
+  const double* rows = (const double*)ctx->vals_e.p;
+  if (ee.sums) {
+    n_rows = (size_t)((bs + nb - 1) / n_traj - bs / n_traj + 1);
+    DTC_HIP(dtc::launch_traj_sum(rows, nb, (int)vs, bs, n_traj, (double*)ctx->vals_f.p,
+                                 ctx->stream));
+    rows = (const double*)ctx->vals_f.p;
+  }
+  DTC_HIP(hipMemcpyAsync(hv_e, rows, n_rows * vs * sizeof(double), hipMemcpyDeviceToHost,
+                         ctx->stream));
+  DTC_HIP(hipStreamSynchronize(ctx->stream));
+  DTC_TRY(settle_pending(ctx));
+  if (ee.sums)
+    energy_sums_out(pr, hv_e, masks, bs, nb, n_traj, pr->t_first, ee.z, ee.zz, ee.x);
+  else
+    energy_rows_out(pr, hv_e, masks, bs, nb, pr->t_first, ee.z, ee.zz, ee.x);
+  return DTC_OK;
+}
 
 int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                   const dtc_device_noise* dv, uint64_t seed, int64_t traj_offset, int32_t n_traj,
@@ -2040,81 +1444,35 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                   const dtc_bond_noise* bond = nullptr, const EchoEnergyOut* ee = nullptr) {
   if (!ctx) return fail(DTC_EINVAL, "null ctx");
   DTC_TRY(check_problem(pr, nz));
-  if (n_traj < 1) return fail(DTC_EINVAL, "n_traj must be >= 1");
-  if (traj_offset < 0) return fail(DTC_EINVAL, "traj_offset must be >= 0");
+  RunCfg rc;
+  DTC_TRY(init_run_cfg(ctx, pr, nz, dv, bond, seed, traj_offset, n_traj,
+                       !dv && !zsite && !use_prefix && !bond && !ee, rc));
   // (the energy echo ignores want_fwd / want_echo: the echo chains only)
   const bool want_fwd = !ee && pr->want_fwd, want_echo = ee || pr->want_echo;
   if (want_fwd && !fwd) return fail(DTC_EINVAL, "want_fwd but fwd is null");
   if (!ee && want_echo && !echo) return fail(DTC_EINVAL, "want_echo but echo is null");
   if (ee && (dv || bond || zsite || use_prefix))
     return fail(DTC_EINVAL, "internal: the energy echo runs depolarizing or noiseless chains only");
-  DTC_HIP(hipSetDevice(ctx->device));
-
-  RunCfg rc;
-  rc.prob = pr;
-  rc.seed = seed;
-  rc.traj_offset = traj_offset;
-  rc.n_traj = n_traj;
-  rc.noisy = nz->p > 0.0 ? 1 : 0;
-  rc.row_kind = classify_rows(pr);
-  {
-    // the 13 / 7 split where its kernels cover every pass: L = 20, unitary
-    // factored kicks (RX / RY rows), the probe measurement only, no prefix
-    bool s13 = ctx->split13 && pr->L == 20 && !dv && !zsite && !use_prefix && !bond && !ee;
-    for (int k : rc.row_kind) s13 = s13 && (k == dtc::kKindRX || k == dtc::kKindRY);
-    rc.pl = make_plan(pr->L, false, s13);
-  }
-  thresholds(nz->p, &rc.thr1, &rc.thr2, &rc.thr3);
-  if (dv) DTC_TRY(setup_device_noise(ctx, pr, dv, rc));
-  if (bond) DTC_TRY(setup_bond_noise(ctx, pr, bond, rc));
   const Plan& pl = rc.pl;
   const int T = pr->T, L = pr->L;
-  const int P = T - 1 + pr->t_offset;
   const bool want_z = zsite != nullptr;
-  const bool want_f = want_fwd || want_z;
   const bool want_e = want_echo;
-  const int n_obs_f = want_z ? 1 + L : 2;
   // energy echo: a chain's row is norm, Z_i | Z_i Z_i+1 | X_i (energy_impl's)
   const int n_v = 3 * L;
-  const int n_obs_e = ee ? n_v : 2;
-  const int meas_f = want_z ? dtc::kMeasSites : dtc::kMeasProbe;
-  const double fac = dv ? dv->anc_factor : std::pow(1.0 - nz->p, (double)nz->n_anc);
-  // read-out: measured = ro_a * a + ro_b (identity without device noise)
-  const double ro_a = dv ? 1.0 - dv->readout_p01 - dv->readout_p10 : 1.0;
-  const double ro_b = dv ? dv->readout_p10 - dv->readout_p01 : 0.0;
+  const int n_obs_f = want_z ? 1 + L : 2, n_obs_e = ee ? n_v : 2;
+  const ReadOut ro{dv ? dv->anc_factor : std::pow(1.0 - nz->p, (double)nz->n_anc),
+                   dv ? 1.0 - dv->readout_p01 - dv->readout_p10 : 1.0,
+                   dv ? dv->readout_p10 - dv->readout_p01 : 0.0};
 
   DTC_TRY(upload_tables(ctx, pr, pl));
 
   // batch size: F (+ E for echo) resident in HBM
   const int64_t S = (int64_t)pr->n_inst * n_traj;
   // continuation of a prefix: periods 1..n_pre come from dtc_prefix_build
-  const int n_pre = use_prefix ? ctx->prefix_periods : 0;
-  if (use_prefix) {
-    if (ctx->prefix_periods < 0) return fail(DTC_EINVAL, "no prefix built");
-    if (ctx->prefix_states != S || ctx->prefix_n_traj != n_traj ||
-        ctx->prefix_traj_offset != traj_offset || ctx->prefix_len != pl.len ||
-        ctx->prefix_device != (dv ? 1 : 0))
-      return fail(DTC_EINVAL, "prefix built for other trajectories / size / noise kind");
-    if (pr->t_first + pr->t_offset <= n_pre || P <= n_pre)
-      return fail(DTC_EINVAL, "prefixed run must measure only after the prefix's periods");
-    if (prefix_hash(pr, n_pre) != ctx->prefix_hash)
-      return fail(DTC_EINVAL, "problem differs from the prefix's in angles or kick rows");
-  }
+  if (use_prefix) DTC_TRY(check_prefix(ctx, pr, rc, S, dv != nullptr));
   const double per_state = (double)pl.len * 16.0 * (want_e ? 2.0 : 1.0);
   int64_t B = pr->batch;
-  if (B <= 0) {
-    size_t free_b = 0, total_b = 0;
-    DTC_HIP(hipMemGetInfo(&free_b, &total_b));
-    free_b += ctx->F.n + ctx->E.n;  // the batch buffers this call may reuse or regrow
-    // small states: ~64 GiB of batch saturates the device; large states
-    // (L >= 24, C4-style instance batches) may use most of the 288 GB
-    double budget = per_state >= (double)(256ull << 20)
-                        ? 0.7 * (double)free_b
-                        : std::min(0.6 * (double)free_b, 64.0 * (1ull << 30));
-    if (ctx->batch_bytes > 0) budget = ctx->batch_bytes;
-    B = (int64_t)(budget / per_state);
-    B = std::max<int64_t>(1, std::min<int64_t>(B, 4096));
-  }
+  if (B <= 0) DTC_TRY(auto_batch(ctx, per_state, ctx->F.n + ctx->E.n, true, B));
   int octet = 0;
   batch_layout(ctx, rc.pl.L_eff, S, B, octet);
   if (use_prefix) {
@@ -2160,14 +1518,10 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   double* const hv_f = ctx->host_f.p;
   double* const hv_e = ctx->host_e.p;
   std::vector<int64_t> masks(B);
-  // wavefront interior of the echo chains: L = 20 in the 12 / 8 plan, unitary
-  // factored kicks, depolarizing noise only, the probe only, no prefix, the
-  // octet layout
-  bool wf_on = ctx->wavefront && L == 20 && !dv && !bond && !zsite && !use_prefix && octet > 0 &&
-               pl.groups.size() == 2 && pl.groups[0].tb == dtc::kTileBits &&
-               pl.groups[0].act == 0xFFF && pl.groups[1].c == 4 && pl.groups[1].s == 12;
-  for (int k : rc.row_kind) wf_on = wf_on && (k == dtc::kKindRX || k == dtc::kKindRY);
+  const SchedReq rq{want_fwd, want_echo, want_z ? dtc::kMeasSites : dtc::kMeasProbe, n_obs_f,
+                    ee != nullptr, use_prefix ? ctx->prefix_periods : 0, octet};
   WfTables wf_tables;
+  std::vector<Launch> sched;
 
   for (int64_t bs = 0; bs < S; bs += B) {
     const int nb = (int)std::min<int64_t>(B, S - bs);
@@ -2196,288 +1550,22 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
       DTC_HIP(hipMemsetAsync(ctx->vals_e.p, 0, (size_t)nb * T * n_obs_e * sizeof(double),
                              ctx->stream));
 
-    // DTC_NO_LIGHTCONE=1: keep the chains' last two passes (development A/B)
-    // Bond noise runs the plain chains: the cone tables are per instance, and
-    // the dual fold would conjugate the forward layer's table, where the
-    // chain's first D^* is a noisy layer of its own
-    // The energy echo measures every site: no cone, and the trailing kick-only
-    // pass stays (every site's last kick matters)
-    const bool lc_enabled = ctx->lightcone && !rc.bond && !ee;
-    const bool dual_enabled = ctx->dual && !rc.bond;
-    // Forward chain K_1 D K_2 D ... K_P D; after each D_p: measure t = p - t_offset
-    // and branch the echo at t off F.  The whole batch schedule is built first.
-    // Device-like noise (r5): the forward runs one kick layer ahead, one pass
-    // per period as in the unitary case, when every echo chain's first pass
-    // folds into the forward's dual pass -- the chain's echo start is then
-    // taken before that layer, so the layer (a Kraus kick, not invertible) is
-    // never undone; if any chain does not fold, the schedule is rebuilt with
-    // K-D forward passes (two passes per period, nothing run ahead).
-    std::vector<Launch> sched;
-    // energy echo: every (t, group) X and every t's Z row assigned exactly once
-    const int n_grp = (int)pl.groups.size();
-    std::vector<char> x_done(ee ? (size_t)T * n_grp : 0, 0), z_done(ee ? T : 0, 0);
-    // (with bond noise: plain chains, K-D forward passes, nothing runs ahead)
-    bool dev_ahead = rc.device && ctx->dual && ctx->runahead && !rc.bond;
-    for (;;) {
-    sched.clear();
-    bool all_folded = true;
-    const bool dev_kd = rc.device && !dev_ahead;  // device-like noise, K-D forward
-    if (P > n_pre) {
-      Chain fw = forward_chain(pl, n_pre + 1, P - n_pre, dtc::kStreamForward);
-      fw.post_after_d = !dev_kd;
-      // bond noise: period q's kicks take the outgoing Pauli of layer q - 1
-      if (rc.bond)
-        for (size_t k = 1; k < fw.X.size(); ++k) {
-          fw.X[k].bond_on = 1u;
-          fw.X[k].bond_stream = dtc::kStreamForward;
-          fw.X[k].bond_counter = (uint32_t)(n_pre + k);
-        }
-      // start on a group without the probe site: every echo chain then ends
-      // with its kick-only pass on such a group, which the probe does not need
-      // (two groups: the closing groups alternate with p, see below)
-      fw.prio.resize(pl.groups.size());
-      for (size_t g = 0; g < pl.groups.size(); ++g)
-        fw.prio[g] = (int)g + (((group_bits(pl.groups[g]) >> pr->probe_site) & 1ull)
-                                   ? (int)pl.groups.size() : 0);
-      while (!fw.done()) {
-        PassSpec ps = next_pass(fw);
-        const int p = ps.d_index + n_pre;  // the chain counts its own periods
-        const int t = p - pr->t_offset;
-        const bool closes = ps.diag != dtc::kDiagNone;
-        const bool meas = closes && want_f && t >= 0 && t >= pr->t_first;
-        sched.push_back(Launch{ps, sched.empty() ? F0 : F, F, meas ? meas_f : dtc::kMeasNone, 0,
-                               n_obs_f,
-                               meas ? (double*)ctx->vals_f.p + (size_t)t * n_obs_f : nullptr,
-                               (int64_t)T * n_obs_f});
-        if (rc.bond && closes) {
-          sched.back().bond_diag = 1;
-          sched.back().bond_stream = dtc::kStreamForward;
-          sched.back().bond_counter = (uint32_t)p;
-        }
-        if (!closes || !want_e || t < 0 || t < pr->t_first) continue;
-        std::vector<int> ahead(pl.groups.size());
-        for (size_t g = 0; g < pl.groups.size(); ++g) ahead[g] = fw.kc[g] > ps.d_index;
-        Chain ec = echo_chain(pl, p, (uint32_t)(1 + t), ahead);
-        if (rc.bond) {
-          // The echo starts from P_t D'_t ...: on a group that ran ahead, F
-          // holds K_{p+1} P_t and X_0's undo (without the Pauli) leaves P_t; on
-          // the others X_0 is P_t alone (patched below).  Step k's kicks take
-          // the outgoing Pauli of the chain's k-th noisy D^*.
-          std::fill(ec.kc.begin(), ec.kc.end(), 0);
-          if (pl.groups.size() == 2) {
-            // the chain's p + 2 passes alternate between the two groups from its
-            // kick-only first pass: start so that the trailing kick-only pass lands
-            // on the group without the probe, where it is dropped (below)
-            const int gp = ((group_bits(pl.groups[0]) >> pr->probe_site) & 1ull) ? 0 : 1;
-            ec.prio.assign(2, 1);
-            ec.prio[(p % 2) ? 1 - gp : gp] = 0;
-          }
-          for (size_t k = 1; k < ec.X.size(); ++k) {
-            ec.X[k].bond_on = 1u;
-            ec.X[k].bond_stream = (uint32_t)(1 + t);
-            ec.X[k].bond_counter = (uint32_t)k;
-          }
-        }
-        // run ahead under device-like noise, a chain whose first pass undoes
-        // the forward's run-ahead layer must fold (the undo of a Kraus kick
-        // cannot run); the sweep's last chain, after a K-D, has none
-        bool must_fold = false;
-        for (size_t g = 0; g < pl.groups.size(); ++g) must_fold |= dev_ahead && ahead[g];
-        if (rc.device && ctx->dual) {
-          // device-like noise: the chain starts on the group whose forward
-          // K-D closed the period (the dual pass below)
-          ec.prio.resize(pl.groups.size());
-          for (size_t g = 0; g < pl.groups.size(); ++g)
-            ec.prio[g] = (int)g == ps.group ? -1 : (int)g;
-        }
-        const double2* src = F;
-        const size_t chain0 = sched.size();
-        while (!ec.done()) {
-          PassSpec es = next_pass(ec);
-          if (rc.bond && es.pre.enabled && es.pre.mode == dtc::kKickUndo && !ahead[es.group]) {
-            es.pre.mode = dtc::kKickBondPauli;
-            es.pre.row = p - 1;
-            es.pre.bond_on = 1u;
-            es.pre.bond_stream = dtc::kStreamForward;
-            es.pre.bond_counter = (uint32_t)p;
-          }
-          sched.push_back(Launch{es, src, E, dtc::kMeasNone, 1, 2, nullptr, (int64_t)T * 2});
-          if (ee && ec.kc[es.group] == ec.n() + 1 && (es.pre.enabled || es.post.enabled)) {
-            // the pass that applies the group's last kick layer K'_1 -- the
-            // post-kick of a K-D-K / D-K or the kick of a kick-only pass --
-            // measures X of the group's sites after it
-            const int shp = pass_shape(es);
-            const bool last_is_post = shp == dtc::kShapeKDK || shp == dtc::kShapeDK;
-            if (!(last_is_post || shp == dtc::kShapeK) || x_done[(size_t)t * n_grp + es.group])
-              return fail(DTC_EINVAL, "internal: dtc_energy_echo: a group ends in another shape");
-            x_done[(size_t)t * n_grp + es.group] = 1;
-            Launch& l = sched.back();
-            l.meas_mode = dtc::kMeasEnergy;
-            l.meas_at_end = last_is_post ? 1 : 0;  // (a kick-only pass: after its kicks, mid-pass)
-            l.n_obs = n_v;
-            l.meas_stride = (int64_t)T * n_v;
-            l.meas_parts = dtc::kPartXEnd;
-            l.energy_row = (double*)ctx->vals_e.p + (size_t)t * n_v;
-          }
-          if (rc.bond && es.diag != dtc::kDiagNone) {
-            sched.back().bond_diag = 1;
-            sched.back().bond_stream = (uint32_t)(1 + t);
-            sched.back().bond_counter = (uint32_t)es.d_index;
-            sched.back().bond_inv = 1;
-          }
-          src = E;
-        }
-        // A chain that ends with a kick-only pass on a group without the probe
-        // site: unitary single-site kicks on other sites leave <Z_j> unchanged
-        // (K_i^+ Z_j K_i = Z_j), so that pass is dropped and the probe is read
-        // after the previous one.  Not for device-like noise: its Kraus kicks
-        // are not unitary and change the trajectory weight.
-        if (!rc.device && !ee && sched.size() - chain0 >= 2) {
-          const Launch& l = sched.back();
-          const bool kick_only = l.ps.diag == dtc::kDiagNone && !l.ps.post.enabled;
-          if (kick_only && !((group_bits(pl.groups[l.ps.group]) >> pr->probe_site) & 1ull))
-            sched.pop_back();
-        }
-        // Light cone of <Z_j> through the chain's last kick layers (unitary
-        // single-site kicks, D diagonal with nearest-neighbour couplings): the
-        // last layer X_n matters only on j, X_{n-1} on j-1..j+1, X_{n-r} on
-        // j-r..j+r.  The chain's last k passes (k = 4 .. 2, the most that fit)
-        // become one measure-only pass over a tile holding the 8-site window
-        // of the kicks left: their layers, restricted to the cone, with D*
-        // between them, then the probe.
-        if (!rc.device && lc_enabled && sched.size() - chain0 >= 2)
-          lc_merge(rc, sched, chain0, pr->probe_site, ctx->lc_wide, ctx->lc_wide3);
-        if (ee) {
-          // the chain's last pass: norm, Z, ZZ of all sites after its kicks
-          Launch& l = sched.back();
-          if (!(l.meas_parts & dtc::kPartXEnd) || z_done[t])
-            return fail(DTC_EINVAL, "internal: dtc_energy_echo: the chain's last pass ends no group");
-          z_done[t] = 1;
-          l.meas_parts |= dtc::kPartZ;
-        } else {
-          sched.back().meas_mode = dtc::kMeasProbe;
-          sched.back().meas_out = (double*)ctx->vals_e.p + (size_t)t * 2;
-        }
-        // the echo state is only measured: the chain's last pass reads its
-        // tiles and stores nothing (the next chain starts from F again)
-        sched.back().no_store = 1;
-        // Dual pass: the forward K-D-K on G just before the chain computes
-        // K_{p+1} D K_p (input); the chain's first pass, on the same G, is
-        // undo(K_{p+1}) D^* K'_1 of that -- so K'_1 K_p (input), which the
-        // forward pass forms from its own tile after the pre-kick and stores
-        // to E: the chain's first read of F and its own pass go away (48 B
-        // per amplitude instead of 64).  Not when the chain is one pass (the
-        // light-cone end reads F itself).
-        // Device-like noise (no forward layer runs ahead): the forward K-D
-        // on G gives D_p K_p (input), the chain's first pass is D^* K'_1 of
-        // that on G -- K'_1 K_p (input) again, formed by a K-D dual pass.
-        if (dual_enabled && sched.size() - chain0 >= 2 && chain0 >= 1) {
-          Launch& f = sched[chain0 - 1];
-          const Launch& e = sched[chain0];
-          const int fs = dev_kd ? dtc::kShapeKD : dtc::kShapeKDK;
-          const int es = dev_kd ? dtc::kShapeDK : dtc::kShapeKDK;
-          // (the dual kernels carry the probe at most: not with per-site Z)
-          const bool fok = pass_shape(f.ps) == fs && !f.basis && f.src == F &&
-                           pl.groups[f.ps.group].tb == dtc::kTileBits &&
-                           (f.meas_mode == dtc::kMeasNone || f.meas_mode == dtc::kMeasProbe);
-          const bool eok =
-              pass_shape(e.ps) == es && e.ps.lc_w0 < 0 && e.ps.group == f.ps.group &&
-              e.ps.post.enabled && !e.meas_parts &&
-              (dev_kd ? e.ps.post.skip == 0 && f.ps.pre.skip == 0
-                      : e.ps.pre.mode == dtc::kKickUndo && e.ps.pre.skip == 0 &&
-                            f.ps.post.skip == 0);
-          // the fold is exact only when the chain's first pass conjugates the
-          // forward's diagonal (one table per instance; d_index only counts
-          // each chain's own periods) and, in the unitary case, undoes exactly
-          // the forward's post-kick: check it, so a different chain order
-          // falls back to the separate passes instead of folding wrongly
-          const bool same_d = f.ps.diag == dtc::kDiagFwd && e.ps.diag == dtc::kDiagConj;
-          const bool undoes_post =
-              dev_kd || (f.ps.post.enabled && f.ps.post.mode == dtc::kKickForward &&
-                            e.ps.pre.row == f.ps.post.row &&
-                            e.ps.pre.stream == f.ps.post.stream &&
-                            e.ps.pre.rng_period == f.ps.post.rng_period);
-          const int fk = (fok && same_d && undoes_post) ? pass_kind(rc, f.ps, fs) : -1;
-          const bool kind_ok = rc.device ? (fk == dtc::kKindRXU || fk == dtc::kKindRYU ||
-                                            fk == dtc::kKindGen)
-                                         : (fk == dtc::kKindRX || fk == dtc::kKindRY ||
-                                            fk == dtc::kKindGen);
-          const PassSpec branch{f.ps.group, f.ps.pre, e.ps.post, dtc::kDiagNone, 0};
-          // (run ahead under device-like noise, the chain's first pass holds an
-          // undo of a Kraus kick: its own kind is not a factored one, and it
-          // never runs)
-          if (fok && eok && kind_ok && (dev_ahead || fk == pass_kind(rc, e.ps, es)) &&
-              fk == pass_kind(rc, branch, -1)) {
-            f.ps2 = branch;
-            f.dst2 = E;
-            sched.erase(sched.begin() + (std::ptrdiff_t)chain0);
-          } else if (must_fold) {
-            all_folded = false;
-          }
-        } else if (must_fold) {
-          all_folded = false;
-        }
-        // Wavefront interior: the run of plain stored K-D-K launches between
-        // the chain's first pass (here or folded into the forward's dual pass)
-        // and its end becomes the planner's deeper passes over tiles that
-        // share site 11 (dtc_wavefront.h): fewer passes over the state
-        if (wf_on && sched.size() > chain0) {
-          const bool folded = chain0 >= 1 && sched[chain0 - 1].dst2 == E &&
-                              sched[chain0].src == E;
-          const size_t r0 = folded ? chain0 : chain0 + 1;
-          size_t r1 = sched.size() - 1;  // the chain's end (measure-only)
-          // (energy echo: the end is every group's last pass, the run stops
-          // before the first of them)
-          for (size_t i = chain0; ee && i < r1; ++i)
-            if (sched[i].meas_parts) r1 = i;
-          if (r1 > r0) wf_replace(ctx, rc, sched, r0, r1, wf_tables);
-        }
-      }
-    }
-    if (!dev_ahead || all_folded) break;
-    dev_ahead = false;
-    if (ctx->verbose)
+    // the whole batch schedule is built first (dtc_schedule.h), once per batch
+    const SchedBufs bufs{F0, F, E, (double*)ctx->vals_f.p, (double*)ctx->vals_e.p};
+    SchedInfo info;
+    if (const char* err = build_autocorr_schedule(rc, ctx->so, rq, bufs, wf_tables, sched, info))
+      return fail(DTC_EINVAL, err);
+    if (info.rebuilt && ctx->verbose)
       std::fprintf(stderr, "[dtc] device-noise schedule rebuilt with K-D forward passes "
                            "(an echo chain did not fold into the dual pass)\n");
-    }
-    for (int t = std::max(0, pr->t_first); ee && t < T; ++t) {
-      if (t + pr->t_offset == 0) continue;
-      bool all = z_done[t] != 0;
-      for (int g = 0; g < n_grp; ++g) all = all && x_done[(size_t)t * n_grp + g];
-      if (!all) return fail(DTC_EINVAL, "internal: dtc_energy_echo left a time row unmeasured");
-    }
-    for (const Launch& l : sched) ctx->sched_counts[0] += l.dst2 != nullptr;
-    if (rc.device) ++ctx->sched_counts[dev_ahead ? 1 : 2];
+    ctx->sched_counts[0] += info.n_folds;
+    if (rc.device) ++ctx->sched_counts[info.dev_ahead ? 1 : 2];
     if (pl.groups[0].tb == dtc::kMaxTileBits) ++ctx->sched_counts[3];
-    if (wf_tables.dirty) {
-      // new table sets (the first batch's schedule): the stream is idle here
-      DTC_HIP(hipStreamSynchronize(ctx->stream));
-      DTC_TRY(ensure(ctx->wf_tab, wf_tables.host.size() * sizeof(double)));
-      DTC_HIP(hipMemcpy(ctx->wf_tab.p, wf_tables.host.data(),
-                        wf_tables.host.size() * sizeof(double), hipMemcpyHostToDevice));
-      wf_tables.dirty = false;
-    }
+    DTC_TRY(upload_wf_tables(ctx, wf_tables));
     if (!use_prefix) DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, octet));
     DTC_TRY(run_launches(ctx, rc, bs, nb, sched));
     if (ee) {
-      // rows, or their per-instance sums (traj_sum_kernel, as dtc_energy_sums)
-      const size_t vs = (size_t)T * n_v;
-      size_t n_rows = (size_t)nb;
-      const double* rows = (const double*)ctx->vals_e.p;
-      if (ee->sums) {
-        n_rows = (size_t)((bs + nb - 1) / n_traj - bs / n_traj + 1);
-        DTC_HIP(dtc::launch_traj_sum(rows, nb, (int)vs, bs, n_traj, (double*)ctx->vals_f.p,
-                                     ctx->stream));
-        rows = (const double*)ctx->vals_f.p;
-      }
-      DTC_HIP(hipMemcpyAsync(hv_e, rows, n_rows * vs * sizeof(double), hipMemcpyDeviceToHost,
-                             ctx->stream));
-      DTC_HIP(hipStreamSynchronize(ctx->stream));
-      DTC_TRY(settle_pending(ctx));
-      if (ee->sums)
-        energy_sums_out(pr, hv_e, masks.data(), bs, nb, n_traj, pr->t_first, ee->z, ee->zz, ee->x);
-      else
-        energy_rows_out(pr, hv_e, masks.data(), bs, nb, pr->t_first, ee->z, ee->zz, ee->x);
+      DTC_TRY(energy_echo_out(ctx, pr, *ee, masks.data(), bs, nb, n_traj, hv_e));
       continue;
     }
     DTC_HIP(hipMemcpyAsync(hv_f, ctx->vals_f.p, (size_t)nb * T * n_obs_f * sizeof(double),
@@ -2487,37 +1575,8 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                              hipMemcpyDeviceToHost, ctx->stream));
     DTC_HIP(hipStreamSynchronize(ctx->stream));
     DTC_TRY(settle_pending(ctx));
-
-    const int j = pr->probe_site;
-    for (int b = 0; b < nb; ++b) {
-      const int64_t g = bs + b;
-      const uint64_t m = (uint64_t)masks[b];
-      const double zinit = ((m >> j) & 1ull) ? -1.0 : 1.0;
-      for (int t = std::max(0, pr->t_first); t < T; ++t) {
-        const bool at_init = (t + pr->t_offset == 0);
-        const double* vf = hv_f + ((size_t)b * T + t) * n_obs_f;
-        // bond noise: the forward state at t is measured before its layer's
-        // outgoing Pauli P_t, whose X content flips the sign of <Z_i>
-        const uint64_t px =
-            (rc.bond && !at_init)
-                ? bond_out_x(rc, (uint64_t)(traj_offset + g % n_traj), dtc::kStreamForward,
-                             (uint32_t)(t + pr->t_offset))
-                : 0ull;
-        const double zj_f = (at_init ? zinit : (want_z ? vf[1 + j] : vf[1])) *
-                            (((px >> j) & 1ull) ? -1.0 : 1.0);
-        if (want_fwd) fwd[(size_t)g * T + t] = ro_a * (fac * zinit * zj_f) + ro_b;
-        if (want_z) {
-          double* zo = zsite + ((size_t)g * T + t) * L;
-          for (int i = 0; i < L; ++i)
-            zo[i] = at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0)
-                            : (((px >> i) & 1ull) ? -vf[1 + i] : vf[1 + i]);
-        }
-        if (want_e) {
-          const double zj_e = at_init ? zinit : hv_e[((size_t)b * T + t) * 2 + 1];
-          echo[(size_t)g * T + t] = ro_a * (fac * zinit * zj_e) + ro_b;
-        }
-      }
-    }
+    autocorr_rows_out(rc, ro, hv_f, hv_e, masks.data(), bs, nb, want_fwd ? fwd : nullptr,
+                      want_e ? echo : nullptr, zsite);
   }
   return DTC_OK;
 }
@@ -2530,21 +1589,10 @@ int prefix_build_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                       int32_t n_traj, int32_t n_periods) {
   if (!ctx) return fail(DTC_EINVAL, "null ctx");
   DTC_TRY(check_problem(pr, nz));
-  if (n_traj < 1) return fail(DTC_EINVAL, "n_traj must be >= 1");
-  if (traj_offset < 0) return fail(DTC_EINVAL, "traj_offset must be >= 0");
+  RunCfg rc;
+  DTC_TRY(init_run_cfg(ctx, pr, nz, dv, nullptr, seed, traj_offset, n_traj, false, rc));
   if (n_periods < 1 || n_periods > pr->T - 1 + pr->t_offset)
     return fail(DTC_EINVAL, "n_periods must be in [1, T - 1 + t_offset]");
-  DTC_HIP(hipSetDevice(ctx->device));
-  RunCfg rc;
-  rc.prob = pr;
-  rc.pl = make_plan(pr->L);
-  rc.seed = seed;
-  rc.traj_offset = traj_offset;
-  rc.n_traj = n_traj;
-  rc.noisy = nz->p > 0.0 ? 1 : 0;
-  rc.row_kind = classify_rows(pr);
-  thresholds(nz->p, &rc.thr1, &rc.thr2, &rc.thr3);
-  if (dv) DTC_TRY(setup_device_noise(ctx, pr, dv, rc));
   const Plan& pl = rc.pl;
   DTC_TRY(upload_tables(ctx, pr, pl));
   const int64_t S = (int64_t)pr->n_inst * n_traj;
@@ -2770,78 +1818,7 @@ int dtc_apply_periods(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, 
   return DTC_OK;
 }
 
-
 namespace {
-
-// A batch's finished rows hv[nb][T][3 L] (norm, Z_i | Z_i Z_i+1 | X_i per time)
-// into the caller's per-trajectory arrays; the row of the initial time is
-// formed from the state's mask.  Rows before t_first (dtc_energy_echo: their
-// chains are not built) are left 0.
-void energy_rows_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
-                     int nb, int t_first, double* z, double* zz, double* x) {
-  const int T = pr->T, L = pr->L, n_v = 3 * L;
-  for (int b = 0; b < nb; ++b) {
-    const int64_t g = bs + b;
-    const uint64_t m = (uint64_t)masks[b];
-    for (int t = 0; t < T; ++t) {
-      const bool at_init = (t + pr->t_offset == 0), skip = t < t_first;
-      const double* vf = hv + ((size_t)b * T + t) * n_v;
-      const double* vx = vf + 2 * L - 1;  // X_i at vx[1 + i]
-      double* zo = z + ((size_t)g * T + t) * L;
-      double* xo = x + ((size_t)g * T + t) * L;
-      for (int i = 0; i < L; ++i) {
-        zo[i] = skip ? 0.0 : (at_init ? (((m >> i) & 1ull) ? -1.0 : 1.0) : vf[1 + i]);
-        xo[i] = (skip || at_init) ? 0.0 : vx[1 + i];
-      }
-      if (L > 1) {
-        double* zzo = zz + ((size_t)g * T + t) * (L - 1);
-        for (int i = 0; i + 1 < L; ++i)
-          zzo[i] = skip ? 0.0
-                        : (at_init ? ((((m >> i) ^ (m >> (i + 1))) & 1ull) ? -1.0 : 1.0)
-                                   : vf[1 + L + i]);
-      }
-    }
-  }
-}
-
-// The same for the per-instance sums of a batch's rows (traj_sum_kernel),
-// hv[instances of the batch][T][3 L], added to the caller's zeroed sums.
-void energy_sums_out(const dtc_problem* pr, const double* hv, const int64_t* masks, int64_t bs,
-                     int nb, int n_traj, int t_first, double* z, double* zz, double* x) {
-  const int T = pr->T, L = pr->L, n_v = 3 * L;
-  const int64_t i0 = bs / n_traj, n_ib = (bs + nb - 1) / n_traj - i0 + 1;
-  for (int64_t i = 0; i < n_ib; ++i) {
-    const int64_t inst = i0 + i;
-    for (int t = t_first; t < T; ++t) {
-      if (t + pr->t_offset == 0) continue;
-      const double* vf = hv + ((size_t)i * T + t) * n_v;
-      const double* vx = vf + 2 * L - 1;
-      double* zo = z + ((size_t)inst * T + t) * L;
-      double* xo = x + ((size_t)inst * T + t) * L;
-      for (int k = 0; k < L; ++k) {
-        zo[k] += vf[1 + k];
-        xo[k] += vx[1 + k];
-      }
-      if (L > 1) {
-        double* zzo = zz + ((size_t)inst * T + t) * (L - 1);
-        for (int k = 0; k + 1 < L; ++k) zzo[k] += vf[1 + L + k];
-      }
-    }
-  }
-  if (pr->t_offset == 0 && t_first == 0) {
-    for (int b = 0; b < nb; ++b) {
-      const int64_t inst = (bs + b) / n_traj;
-      const uint64_t m = (uint64_t)masks[b];
-      double* zo = z + (size_t)inst * T * L;
-      for (int k = 0; k < L; ++k) zo[k] += ((m >> k) & 1ull) ? -1.0 : 1.0;
-      if (L > 1) {
-        double* zzo = zz + (size_t)inst * T * (L - 1);
-        for (int k = 0; k + 1 < L; ++k)
-          zzo[k] += (((m >> k) ^ (m >> (k + 1))) & 1ull) ? -1.0 : 1.0;
-      }
-    }
-  }
-}
 
 // sums: z, zz, x are per-instance sums over the trajectories ([n_inst][T][.],
 // dtc_energy_sums) instead of per-trajectory rows
@@ -2851,21 +1828,8 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                 const dtc_bond_noise* bond = nullptr) {
   if (!ctx || !z || !x || (!zz && pr && pr->L > 1)) return fail(DTC_EINVAL, "null ctx/outputs");
   DTC_TRY(check_problem(pr, nz));
-  if (n_traj < 1) return fail(DTC_EINVAL, "n_traj must be >= 1");
-  if (traj_offset < 0) return fail(DTC_EINVAL, "traj_offset must be >= 0");
-  DTC_HIP(hipSetDevice(ctx->device));
-
   RunCfg rc;
-  rc.prob = pr;
-  rc.pl = make_plan(pr->L);
-  rc.seed = seed;
-  rc.traj_offset = traj_offset;
-  rc.n_traj = n_traj;
-  rc.noisy = nz->p > 0.0 ? 1 : 0;
-  rc.row_kind = classify_rows(pr);
-  thresholds(nz->p, &rc.thr1, &rc.thr2, &rc.thr3);
-  if (dv) DTC_TRY(setup_device_noise(ctx, pr, dv, rc));
-  if (bond) DTC_TRY(setup_bond_noise(ctx, pr, bond, rc));
+  DTC_TRY(init_run_cfg(ctx, pr, nz, dv, bond, seed, traj_offset, n_traj, false, rc));
   const Plan& pl = rc.pl;
   const int T = pr->T, L = pr->L;
   const int P = T - 1 + pr->t_offset;
@@ -2877,14 +1841,10 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   const int64_t S = (int64_t)pr->n_inst * n_traj;
   const double per_state = (double)pl.len * 16.0;
   int64_t B = pr->batch;
-  if (B <= 0) {
-    size_t free_b = 0, total_b = 0;
-    DTC_HIP(hipMemGetInfo(&free_b, &total_b));
-    free_b += ctx->F.n + (dv ? ctx->E.n : 0);
-    const double budget = std::min(0.6 * (double)free_b, 64.0 * (1ull << 30));
-    B = std::max<int64_t>(1, std::min<int64_t>((int64_t)(budget / (dv ? 2 * per_state : per_state)),
-                                               4096));
-  }
+  // (device-like noise: E too, for the X-basis passes)
+  if (B <= 0)
+    DTC_TRY(auto_batch(ctx, dv ? 2 * per_state : per_state, ctx->F.n + (dv ? ctx->E.n : 0), false,
+                       B));
   int octet = 0;
   batch_layout(ctx, rc.pl.L_eff, S, B, octet);
   rc.octet_bits = octet;

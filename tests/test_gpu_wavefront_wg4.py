@@ -134,7 +134,7 @@ def test_wg4_repeatable_and_batch_independent(pkg, monkeypatch, name, p, cap):
 @pytest.mark.parametrize("cap", [None, 2, 3])
 def test_rx_vacuum_t10_plans_no_wavefront_pass(pkg, monkeypatch, cap):
     """Why the RX sweep above has T = 11: at T = 10 its echo chains are too
-    short for the planner to save a launch (wf_replace, csrc/dtc_engine.cpp), so
+    short for the planner to save a launch (wf_replace, csrc/dtc_schedule.h), so
     no wavefront pass runs at any cap and `count > 0` could not hold there.  If
     this starts failing, the planner reaches T = 10 and the RX cases can move
     down to it."""

@@ -2,12 +2,20 @@
 trace (tools/sched_trace.sh) and print per-role launch durations.
 Usage: python tools/sched_join.py gpurun_out/st_<tag> [...]"""
 import collections
+import re
 import sys
 
 import pandas as pd
 
 for base in sys.argv[1:]:
-    sched = [l.split() for l in open(base + ".sched") if l.startswith("sched ")]
+    # the canonical listing (dump_schedule, csrc/dtc_schedule.h): the launch's group,
+    # shape, buffers and measurement mode
+    pat = re.compile(r"shape=(\S+) ps=\[g=(\S+) .*?\] src=([^+ ]+)\S* dst=([^+ ]+)\S* meas=(\d+).* dst2=([^+ ]+)")
+    sched = []
+    for line in open(base + ".sched"):
+        if line.startswith("sched "):
+            shape, g, src, dst, meas, dst2 = pat.search(line).groups()
+            sched.append((g, shape, src + "->" + dst + ("" if dst2 == "-" else "+" + dst2), meas))
     k = pd.read_csv(base + "/kt_kernel_trace.csv").sort_values("Dispatch_Id")
     k = k[~k.Kernel_Name.str.contains("prep|reduce|rocclr|dbg_")]
     assert len(k) % len(sched) == 0, (len(k), len(sched))
@@ -16,6 +24,6 @@ for base in sys.argv[1:]:
     stats = collections.defaultdict(list)
     for i, (n, d) in enumerate(zip(names, dur)):
         f = sched[i % len(sched)]
-        stats[(n, f[2], f[3], f[8], f[9])].append(d)
+        stats[(n, *f)].append(d)
     for key, v in sorted(stats.items()):
         print(base.split("/")[-1], *key, len(v), f"{sum(v) / len(v):.3f} [{min(v):.3f}, {max(v):.3f}]")
