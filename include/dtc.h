@@ -416,11 +416,66 @@ int dtc_energy_echo_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise*
                          uint64_t seed, int64_t traj_offset, int32_t n_traj, double* z_sum,
                          double* zz_sum, double* x_sum);
 
+/* Measurement sampling (additive, ABI 12 unchanged): what a measurement of the
+ * chain itself returns, a bitstring -- the counts BackendEstimatorV2 forms its
+ * expectation values from (...-fast-energy.py:168-171: 4096 shots per commuting
+ * group, the Z-type and the X-type terms of H each in their own basis).  For
+ * every trajectory of dtc_energy and every time t, n_shots outcomes in the Z
+ * basis and n_shots in the X basis of the forward state after p = t + t_offset
+ * periods.
+ *
+ * A sample: for the state psi (2^L amplitudes, site i = bit i) let
+ * S(x) = sum_{y <= x} |psi_y|^2 in ascending index order and W = S(2^L - 1)
+ * (1 up to rounding).  For a uniform u in [0, 1) the Z-basis outcome is the
+ * smallest x with S(x) > u W; the X-basis outcome is the same rule on
+ * H^(x)L psi (a noiseless basis change, as dtc_energy measures X): bit i set
+ * means X_i = -1.  An index of zero weight is never returned.
+ *
+ * The uniforms: Philox4x32-10 with the key of the kick draws and the counter
+ *   c0 = shot | basis << 30   (basis 0 = Z, 1 = X; shot < 2^30),
+ *   c1 = p, c2 = 0xFFFFFFFE (the measurement stream), c3 = (uint32_t)traj,
+ *   u = (((uint64_t)w0 << 21) | (w1 >> 11)) * 2^-53.
+ * No kick, preparation or bond draw has c2 = 0xFFFFFFFE, and the kick draws stay
+ * exactly as they are: a sampled run's trajectories are dtc_energy's, trajectory
+ * for trajectory.  Row p = 0 follows the rule on the prepared basis state: Z
+ * gives the (noisily) prepared mask, X gives floor(u 2^L).
+ *
+ * Rows are bit-identical for any batch size, any split of the trajectories and
+ * either batch layout: the sums behind S are formed in a fixed hierarchy over
+ * the logical index (dtc_sample.hip), which agrees with the sequential S of
+ * dtc_sample_state up to rounding of the sums (an outcome may differ only
+ * where u W lies within that rounding of a boundary S(x)).
+ *
+ * The forward runs in K-D passes (after the pass closing period p the state at
+ * p is in memory exactly, nothing runs a kick layer ahead); each sampled state
+ * costs one extra read per basis (the weights; the picks read one 64 KiB chunk
+ * per shot), the X basis one basis-change pass per site group before it.
+ * Launches are counted under DTC_KERNEL_REDUCE when profiling.  Depolarizing or
+ * noiseless kicks only: under device-like noise a shot would have to be
+ * weighted by the Kraus norm, and bond noise has no sampled entry point either
+ * (the Python wrapper refuses both).  The echo state is never stored, so it is
+ * not sampled.
+ *
+ * zbits, xbits: [n_inst][n_traj][T][n_shots] uint64, either may be NULL (not both);
+ * rows t < prob->t_first are left 0; want_fwd / want_echo ignored.
+ * DTC_EINVAL for null arguments, n_shots < 1 and L > 32. */
+int dtc_sample(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise, uint64_t seed,
+               int64_t traj_offset, int32_t n_traj, int32_t n_shots, uint64_t* zbits,
+               uint64_t* xbits);
+/* host only: the uniforms of (seed, traj, p, basis), u[n_shots] */
+int dtc_sample_draws(uint64_t seed, int64_t traj, int32_t p, int32_t basis, int32_t n_shots,
+                     double* u);
+/* host only, the contract's reference: outcomes of n uniforms on a host state of 2^L
+ * complex128 amplitudes (sequential S in index order); basis 1 applies H^L first. */
+int dtc_sample_state(const double* state, int32_t L, int32_t basis, const double* u, int32_t n,
+                     uint64_t* bits);
+
 /* Profiling: when enabled, every kernel launch is bracketed by HIP events on
  * the ctx stream and accumulated per kernel kind. */
 #define DTC_KERNEL_LO_PASS 0   /* fused RZZ+RZ diagonal + low-site kick pass */
 #define DTC_KERNEL_HI_PASS 1   /* high-site kick pass                        */
-#define DTC_KERNEL_REDUCE 2    /* per-state observable reduction; bond-noise sign pass */
+#define DTC_KERNEL_REDUCE 2    /* per-state observable reduction; bond-noise sign pass;
+                                  measurement sampling (weights, picks) */
 #define DTC_KERNEL_INIT 3      /* preparation: bond-noise diagonal table builder */
 #define DTC_KERNEL_FINAL_PASS 4 /* last pass of an echo chain: measure, no store */
 #define DTC_KERNEL_EXCHANGE 5  /* virtual ranks' in-place slice exchange        */

@@ -57,6 +57,9 @@ EXPORTED_SYMBOLS = (
     "dtc_energy_sums_bond",
     "dtc_energy_echo",
     "dtc_energy_echo_sums",
+    "dtc_sample",
+    "dtc_sample_draws",
+    "dtc_sample_state",
 )
 
 KERNEL_LO_PASS = 0
@@ -68,7 +71,8 @@ KERNEL_EXCHANGE = 5
 KERNEL_NAMES = {
     KERNEL_LO_PASS: "pass_kernel<diag>  (fused RZZ+RZ diagonal + sites 0..11 kick)",
     KERNEL_HI_PASS: "pass_kernel<none>  (kick on sites >= 12)",
-    KERNEL_REDUCE: "reduce_kernel, bond_obs_sign_kernel (bond-noise signs of the energy rows)",
+    KERNEL_REDUCE: "reduce_kernel, bond_obs_sign_kernel (bond-noise signs of the energy rows), "
+                   "sample_weights_kernel / sample_pick_kernel (measurement sampling)",
     KERNEL_INIT: "bond_diag_kernel (bond-noise diagonal tables per state, dtc_autocorr_bond)",
     KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split / the last dtc_xend_pass of an energy "
                        "echo chain (measure only, no store)",
@@ -284,6 +288,16 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         ]
         lib.dtc_energy_sums_bond.argtypes = lib.dtc_energy_bond.argtypes
         lib.dtc_plan_groups.argtypes = [ctypes.c_int32, P(ctypes.c_uint64), ctypes.c_int32]
+        lib.dtc_sample.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), ctypes.c_uint64, ctypes.c_int64,
+            ctypes.c_int32, ctypes.c_int32, P(ctypes.c_uint64), P(ctypes.c_uint64),
+        ]
+        lib.dtc_sample_draws.argtypes = [
+            ctypes.c_uint64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp,
+        ]
+        lib.dtc_sample_state.argtypes = [
+            _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, P(ctypes.c_uint64),
+        ]
         for name in EXPORTED_SYMBOLS:
             if name not in ("dtc_last_error", "dtc_abi_version"):
                 getattr(lib, name).restype = ctypes.c_int

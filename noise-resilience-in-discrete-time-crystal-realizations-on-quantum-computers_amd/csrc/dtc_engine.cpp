@@ -90,6 +90,9 @@ struct dtc_ctx {
   // bond noise (dtc_autocorr_bond): draw thresholds [L-1], the angles h | phi of
   // every instance, and the current diagonal layer's per-state factor tables
   DevBuf bond_thr, bond_ang, bond_diag;
+  // measurement sampling (dtc_sample): the chunk weights of the state being
+  // sampled, [batch][n_tiles], and the batch's outcomes, z | x
+  DevBuf sample_w, sample_bits;
   std::vector<dtc::PassKick> pk_host;   // staged pass list (alive until the stream syncs)
   // forward prefix (dtc_prefix_build): every trajectory's state after
   // prefix_periods periods, and what it was built from
@@ -993,6 +996,8 @@ int dtc_close(dtc_ctx* ctx) {
   release(ctx->dev_kraus);
   release(ctx->bond_thr);
   release(ctx->bond_ang);
+  release(ctx->sample_w);
+  release(ctx->sample_bits);
   for (auto& e : ctx->shard_cache) release(e.diag);
   for (auto& e : ctx->shard_maps) release(e.diag);
   release(ctx->shard_kick);
@@ -1014,6 +1019,8 @@ int dtc_release_buffers(dtc_ctx* ctx) {
   release(ctx->recs1);
   release(ctx->pk);
   release(ctx->bond_diag);
+  release(ctx->sample_w);
+  release(ctx->sample_bits);
   return DTC_OK;
 }
 
@@ -2125,6 +2132,218 @@ int dtc_energy_sums_bond(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* n
                          double* x_sum) {
   return energy_bond_impl(ctx, pr, nz, dv, bond, seed, traj_offset, n_traj, z_sum, zz_sum, x_sum,
                           true);
+}
+
+namespace {
+
+// The two sampling launches on a batch's states `st` (F, or E = H^L F) for time
+// row t: weights, then one pick per (state, shot) into out[b][t][.].  Booked
+// under DTC_KERNEL_REDUCE: the weights with the batch's 16 B per amplitude, the
+// pick with the chunk weights and the one chunk each workgroup reads.
+int launch_sample(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
+                  const double2* st, int t, uint32_t basis, int n_shots, uint64_t* out) {
+  dtc::SampleArgs A{};
+  A.state = st;
+  A.weights = (double*)ctx->sample_w.p;
+  A.out = out + (size_t)t * n_shots;
+  A.out_stride = (int64_t)rc.prob->T * n_shots;
+  A.L_eff = rc.pl.L_eff;
+  A.octet_bits = rc.octet_bits;
+  A.batch = batch;
+  A.n_shots = n_shots;
+  A.batch_start = batch_start;
+  A.n_traj = rc.n_traj;
+  A.traj_offset = rc.traj_offset;
+  A.seed = rc.seed;
+  A.period = (uint32_t)(t + rc.prob->t_offset);
+  A.basis = basis;
+  for (int k = 0; k < 2; ++k) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (ctx->prof) {
+      e0 = get_event(ctx);
+      e1 = get_event(ctx);
+      DTC_HIP(hipEventRecord(e0, ctx->stream));
+    }
+    DTC_HIP(k == 0 ? dtc::launch_sample_weights(A, ctx->stream)
+                   : dtc::launch_sample_pick(A, ctx->stream));
+    if (ctx->prof) {
+      DTC_HIP(hipEventRecord(e1, ctx->stream));
+      const double bytes = k == 0 ? 16.0 * (double)rc.pl.len * batch
+                                  : (double)batch * n_shots * (8.0 * rc.pl.n_tiles + 16.0 * dtc::kTile);
+      ctx->pending.push_back(Pending{DTC_KERNEL_REDUCE, e0, e1, bytes});
+    }
+  }
+  return DTC_OK;
+}
+
+}  // namespace
+
+int dtc_sample(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+               int64_t traj_offset, int32_t n_traj, int32_t n_shots, uint64_t* zbits,
+               uint64_t* xbits) {
+  if (!ctx || (!zbits && !xbits)) return fail(DTC_EINVAL, "null ctx/outputs");
+  if (n_shots < 1 || n_shots > (1 << 30))
+    return fail(DTC_EINVAL, "n_shots must be in [1, 2^30]");
+  DTC_TRY(check_problem(pr, nz));
+  RunCfg rc;
+  DTC_TRY(init_run_cfg(ctx, pr, nz, nullptr, nullptr, seed, traj_offset, n_traj, false, rc));
+  const Plan& pl = rc.pl;
+  const int T = pr->T, L = pr->L;
+  const int P = T - 1 + pr->t_offset;
+  const int64_t S = (int64_t)pr->n_inst * n_traj;
+  const size_t row = (size_t)T * n_shots;  // outcomes per state and basis
+  if (zbits) std::fill(zbits, zbits + (size_t)S * row, (uint64_t)0);
+  if (xbits) std::fill(xbits, xbits + (size_t)S * row, (uint64_t)0);
+
+  // Row p = 0: the rule on the prepared basis state |m>.  Z: every outcome is
+  // m.  X: H^L |m> has weight 2^-L on every index, S(x) = (x + 1) 2^-L, so the
+  // outcome is floor(u 2^L) (exact: u is a multiple of 2^-53, L <= 32).
+  if (pr->t_offset == 0 && pr->t_first == 0) {
+    for (int64_t s = 0; s < S; ++s) {
+      const uint64_t traj = (uint64_t)(traj_offset + s % n_traj);
+      const uint64_t m = init_state_mask(rc, traj);
+      for (int k = 0; k < n_shots; ++k) {
+        if (zbits) zbits[(size_t)s * row + k] = m;
+        if (xbits)
+          xbits[(size_t)s * row + k] =
+              (uint64_t)std::floor(std::ldexp(dtc::sample_uniform(seed, traj, 0u, 1u, (uint32_t)k), L));
+      }
+    }
+  }
+  if (P == 0) return DTC_OK;
+  DTC_TRY(upload_tables(ctx, pr, pl));
+
+  const double per_state = (double)pl.len * 16.0 * (xbits ? 2.0 : 1.0);
+  int64_t B = pr->batch;
+  if (B <= 0) DTC_TRY(auto_batch(ctx, per_state, ctx->F.n + (xbits ? ctx->E.n : 0), false, B));
+  // (the outcomes of a batch: at most 1 GiB)
+  B = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)((size_t)(1u << 27) / row / 2)));
+  int octet = 0;
+  batch_layout(ctx, pl.L_eff, S, B, octet);
+  rc.octet_bits = octet;
+  const int64_t Bp = dtc::octet_padded(B, octet);
+  DTC_TRY(ensure(ctx->F, (size_t)(Bp * pl.len * 16)));
+  if (xbits) DTC_TRY(ensure(ctx->E, (size_t)(Bp * pl.len * 16)));
+  DTC_TRY(ensure(ctx->basis, (size_t)B * sizeof(int64_t)));
+  DTC_TRY(ensure(ctx->sample_w, (size_t)B * pl.n_tiles * sizeof(double)));
+  DTC_TRY(ensure(ctx->sample_bits, 2 * (size_t)B * row * sizeof(uint64_t)));
+  std::vector<int64_t> masks(B);
+
+  // The schedule: the forward chain in K-D passes (post_after_d = false: no
+  // pass that applies D starts the next kick layer), so after the pass closing
+  // period p the state in F is exactly the state at p, as energy_impl keeps it
+  // under device-like noise -- here with the unitary kick kinds.
+  struct SPass {
+    PassSpec ps;
+    int t;  // the time this pass completes (sampled after it), or -1
+    const int64_t* basis = nullptr;
+  };
+  std::vector<SPass> sched;
+  {
+    Chain fw = forward_chain(pl, 1, P, dtc::kStreamForward);
+    fw.post_after_d = false;
+    while (!fw.done()) {
+      SPass e{next_pass(fw), -1};
+      if (e.ps.diag != dtc::kDiagNone) {
+        const int t = e.ps.d_index - pr->t_offset;
+        if (t >= pr->t_first && t < T) e.t = t;
+      }
+      sched.push_back(e);
+    }
+  }
+
+  for (int64_t bs = 0; bs < S; bs += B) {
+    const int nb = (int)std::min<int64_t>(B, S - bs);
+    for (int b = 0; b < nb; ++b)
+      masks[b] = (int64_t)init_state_mask(rc, (uint64_t)(traj_offset + (bs + b) % n_traj));
+    double2* F = (double2*)ctx->F.p;
+    double2* E = (double2*)ctx->E.p;
+    uint64_t* zb = (uint64_t*)ctx->sample_bits.p;
+    uint64_t* xb = zb + (size_t)B * row;
+    DTC_HIP(hipMemcpyAsync(ctx->basis.p, masks.data(), nb * sizeof(int64_t),
+                           hipMemcpyHostToDevice, ctx->stream));
+    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, octet));
+    for (const SPass& e : sched) {
+      DTC_TRY(launch_pass_spec(ctx, rc, bs, nb, e.ps, F, F, dtc::kMeasNone, 0, 0, nullptr, 0,
+                               nullptr, 0, 0, e.basis));
+      if (e.t < 0) continue;
+      if (zbits) DTC_TRY(launch_sample(ctx, rc, bs, nb, F, e.t, 0u, n_shots, zb));
+      if (xbits) {
+        // E = H^L F: one noiseless basis-change pass per site group
+        const int G = (int)pl.groups.size();
+        for (int g = 0; g < G; ++g) {
+          PassSpec xs{g, no_kick(), no_kick(), dtc::kDiagNone, 0};
+          xs.pre = dtc::KickDesc{1, 0, dtc::kKickBasisX, 0u, 0u, 0u};
+          DTC_TRY(launch_pass_spec(ctx, rc, bs, nb, xs, g == 0 ? F : E, E, dtc::kMeasNone, 0, 0,
+                                   nullptr, 0));
+        }
+        DTC_TRY(launch_sample(ctx, rc, bs, nb, E, e.t, 1u, n_shots, xb));
+      }
+    }
+    // rows the device did not write (t < t_first, and p = 0, formed above) are
+    // kept: only the sampled rows are copied out
+    const int t0 = std::max(pr->t_first, pr->t_offset == 0 ? 1 : 0);
+    for (int k = 0; k < 2; ++k) {
+      uint64_t* out = k == 0 ? zbits : xbits;
+      if (!out || t0 >= T) continue;
+      DTC_HIP(hipMemcpy2DAsync(out + (size_t)bs * row + (size_t)t0 * n_shots,
+                               row * sizeof(uint64_t),
+                               (k == 0 ? zb : xb) + (size_t)t0 * n_shots, row * sizeof(uint64_t),
+                               (size_t)(T - t0) * n_shots * sizeof(uint64_t), (size_t)nb,
+                               hipMemcpyDeviceToHost, ctx->stream));
+    }
+    DTC_HIP(hipStreamSynchronize(ctx->stream));
+    DTC_TRY(settle_pending(ctx));
+  }
+  return DTC_OK;
+}
+
+int dtc_sample_draws(uint64_t seed, int64_t traj, int32_t p, int32_t basis, int32_t n_shots,
+                     double* u) {
+  if (!u) return fail(DTC_EINVAL, "null output");
+  if (n_shots < 1 || traj < 0 || p < 0 || basis < 0 || basis > 1)
+    return fail(DTC_EINVAL, "dtc_sample_draws: n_shots >= 1, traj >= 0, p >= 0, basis 0 or 1");
+  for (int32_t k = 0; k < n_shots; ++k)
+    u[k] = dtc::sample_uniform(seed, (uint64_t)traj, (uint32_t)p, (uint32_t)basis, (uint32_t)k);
+  return DTC_OK;
+}
+
+int dtc_sample_state(const double* state, int32_t L, int32_t basis, const double* u, int32_t n,
+                     uint64_t* bits) {
+  if (!state || !u || !bits) return fail(DTC_EINVAL, "null argument");
+  if (L < 1 || L > 32) return fail(DTC_EINVAL, "L must be in [1, 32]");
+  if (n < 1 || basis < 0 || basis > 1) return fail(DTC_EINVAL, "n >= 1, basis 0 or 1");
+  const size_t N = (size_t)1 << L;
+  std::vector<double> cum(N);
+  if (basis == 0) {
+    for (size_t x = 0; x < N; ++x)
+      cum[x] = state[2 * x] * state[2 * x] + state[2 * x + 1] * state[2 * x + 1];
+  } else {
+    // H on every site: Walsh-Hadamard butterflies, one factor 2^(-L/2) at the end
+    std::vector<double> a(state, state + 2 * N);
+    for (size_t h = 1; h < N; h <<= 1)
+      for (size_t i = 0; i < N; i += 2 * h)
+        for (size_t j = i; j < i + h; ++j)
+          for (int c = 0; c < 2; ++c) {
+            const double p0 = a[2 * j + c], p1 = a[2 * (j + h) + c];
+            a[2 * j + c] = p0 + p1;
+            a[2 * (j + h) + c] = p0 - p1;
+          }
+    const double f = std::ldexp(1.0, -L);
+    for (size_t x = 0; x < N; ++x) cum[x] = f * (a[2 * x] * a[2 * x] + a[2 * x + 1] * a[2 * x + 1]);
+  }
+  // S in index order; the last index of non-zero weight where u W rounds up to W
+  size_t last = 0;
+  for (size_t x = 0; x < N; ++x)
+    if (cum[x] > 0.0) last = x;
+  for (size_t x = 1; x < N; ++x) cum[x] += cum[x - 1];
+  const double W = cum[N - 1];
+  for (int32_t k = 0; k < n; ++k) {
+    if (!(u[k] >= 0.0 && u[k] < 1.0)) return fail(DTC_EINVAL, "uniforms must lie in [0, 1)");
+    const size_t x = (size_t)(std::upper_bound(cum.begin(), cum.end(), u[k] * W) - cum.begin());
+    bits[k] = (uint64_t)(x < N ? x : last);
+  }
+  return DTC_OK;
 }
 
 int32_t dtc_plan_groups(int32_t n_bits, uint64_t* masks, int32_t max_groups) {

@@ -479,4 +479,30 @@ hipError_t launch_kick_swap(const PassArgs& a, int k_bits, int kind, hipStream_t
 hipError_t launch_exchange_swap(double2* state, int nl, int k, int nsub, int slice,
                                 hipStream_t stream);
 
+// Measurement sampling (dtc_sample.hip; include/dtc.h dtc_sample): n_shots
+// outcomes per state of the rule "smallest x with S(x) > u W" over |a_x|^2.
+// Two launches per sampled batch and basis:
+//  * weights: one read-only sweep of the batch, w[b][c] = sum |a|^2 over the
+//    chunk of kTile consecutive logical amplitudes c (a fixed reduction tree
+//    over the logical index: the same bits in either batch layout);
+//  * pick: one workgroup per (state, shot) narrows [0, 2^L_eff) to one index,
+//    first over the chunk weights, then over the chosen chunk's amplitudes.
+// The uniform of (state, shot) is dtc_rng.h sample_uniform(seed, traj, period,
+// basis, shot); out[b * out_stride + shot] receives the index.
+struct SampleArgs {
+  const double2* state;    // the batch, in the layout of octet_bits
+  double* weights;         // [batch][2^(L_eff - kTileBits)]
+  uint64_t* out;           // [batch] rows of n_shots, out_stride apart
+  int64_t out_stride;
+  int L_eff, octet_bits;
+  int batch, n_shots;
+  int64_t batch_start;
+  int n_traj;
+  int64_t traj_offset;
+  uint64_t seed;
+  uint32_t period, basis;
+};
+hipError_t launch_sample_weights(const SampleArgs& a, hipStream_t stream);
+hipError_t launch_sample_pick(const SampleArgs& a, hipStream_t stream);
+
 }  // namespace dtc

@@ -23,6 +23,10 @@ namespace dtc {
 static constexpr uint32_t kStreamForward = 0u;       // forward trajectory
 // echo branch at time index t uses stream 1 + t
 static constexpr uint32_t kStreamPrep = 0xFFFFFFFFu; // neel X-gate prep noise
+// measurement sampling (sample_uniform below).  No kick, preparation or bond
+// draw uses this stream: the forward is stream 0, the echo at t stream 1 + t
+// (t < 2^31), the preparation 0xFFFFFFFF; a bond draw takes its kick layer's.
+static constexpr uint32_t kStreamMeasure = 0xFFFFFFFEu;
 
 DTC_HD void mulhilo32(uint32_t a, uint32_t b, uint32_t* hi, uint32_t* lo) {
   uint64_t p = (uint64_t)a * (uint64_t)b;
@@ -101,6 +105,17 @@ DTC_HD int sample_bond(uint64_t seed, uint64_t traj, uint32_t stream, uint32_t c
              (uint32_t)(seed >> 32) ^ (uint32_t)(traj >> 32), &x, &y);
   if (x >= thr) return 0;
   return 1 + (int)(((uint64_t)y * 15u) >> 32);
+}
+
+// The uniform in [0, 1) of measurement shot `shot` (< 2^30) in basis `basis`
+// (0 = Z, 1 = X) of trajectory `traj` after `period` periods: 53 bits of words
+// 0 and 1, with the key of the kick draws (include/dtc.h dtc_sample).
+DTC_HD double sample_uniform(uint64_t seed, uint64_t traj, uint32_t period, uint32_t basis,
+                             uint32_t shot) {
+  uint32_t x, y;
+  philox_w01(shot | (basis << 30), period, kStreamMeasure, (uint32_t)traj, (uint32_t)seed,
+             (uint32_t)(seed >> 32) ^ (uint32_t)(traj >> 32), &x, &y);
+  return (double)(((uint64_t)x << 21) | (uint64_t)(y >> 11)) * 0x1p-53;
 }
 
 // X content (X or Y) of a Pauli code.

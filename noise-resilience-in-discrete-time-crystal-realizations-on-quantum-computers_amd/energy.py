@@ -37,7 +37,10 @@ Noise accumulation (energy.py:212-218): the script adds
 
 Estimator: the reference's ``BackendEstimatorV2`` default precision 1/64
 means 4096 shots per measurement basis; here the trajectory mean (each
-trajectory an exact expectation) estimates the same quantity.
+trajectory an exact expectation) estimates the same quantity.  ``sampled=True``
+(``get_instances_energy_sampled``) forms every expectation value from measured
+bitstrings instead (``DtcEngine.sample``: one noisy trajectory and one outcome
+per shot and basis), with the estimator's shot noise.
 """
 from __future__ import annotations
 
@@ -46,7 +49,7 @@ import os
 
 import numpy as np
 
-from .engine import SweepSpec, energy_init_mask, refuse_energy_echo
+from .engine import SweepSpec, energy_init_mask, refuse_energy_echo, refuse_sample
 
 HAMILTONIAN_TYPES = ("full", "z_only", "zz_only", "x_only", "z_zz")
 ESTIMATOR_SHOTS = int(math.ceil(1.0 / 0.015625 ** 2))  # BackendEstimatorV2 default precision
@@ -182,6 +185,71 @@ def _g0(g):
     return float(g[0]) if isinstance(g, (list, tuple, np.ndarray)) else float(g)
 
 
+# ---- the sampled estimator (DtcEngine.sample) ----------------------------------
+
+def observables_from_samples(bits_z, bits_x, L: int) -> dict:
+    """The estimator's expectation values from measurement outcomes: ``bits_z``,
+    ``bits_x`` uint64 ``[n_inst][n_traj][T][n_shots]`` (``DtcEngine.sample``; either
+    may be None, its observables are then 0).  Outcome bit i set means the
+    eigenvalue -1 on site i.  Returns the means over trajectories and shots of
+    the +-1 outcomes and their products, ``z`` [n_inst][T][L], ``zz`` [..][L-1]
+    (from the Z-basis outcomes), ``x`` [..][L] -- the shapes ``get_instances_energy``
+    hands to ``energy_from_observables``."""
+    ref = bits_z if bits_z is not None else bits_x
+    if ref is None:
+        raise ValueError("observables_from_samples needs outcomes of at least one basis")
+    n_inst, _, T, _ = np.shape(ref)
+    sites = np.arange(L, dtype=np.uint64)
+
+    def signs(bits):  # [n_inst][n_traj][T][n_shots][L] of +-1
+        b = np.asarray(bits, dtype=np.uint64)
+        return 1.0 - 2.0 * ((b[..., None] >> sites) & np.uint64(1)).astype(np.float64)
+
+    out = {"z": np.zeros((n_inst, T, L)), "zz": np.zeros((n_inst, T, max(L - 1, 0))),
+           "x": np.zeros((n_inst, T, L))}
+    if bits_z is not None:
+        s = signs(bits_z)
+        out["z"] = s.mean(axis=(1, 3))
+        out["zz"] = (s[..., :-1] * s[..., 1:]).mean(axis=(1, 3))
+    if bits_x is not None:
+        out["x"] = signs(bits_x).mean(axis=(1, 3))
+    return out
+
+
+def counts_from_samples(bits, L: int) -> dict:
+    """``{bitstring: count}`` of a flat set of outcomes in qiskit's order (qubit 0
+    is the rightmost character), as ``get_counts`` returns them and the
+    reference's ``compute_z_expectation(counts, num_qubits)`` reads them."""
+    vals, cnt = np.unique(np.asarray(bits, dtype=np.uint64).reshape(-1), return_counts=True)
+    return {format(int(v), f"0{L}b"): int(c) for v, c in zip(vals, cnt)}
+
+
+def get_instances_energy_sampled(spec: SweepSpec, n_traj: int = ESTIMATOR_SHOTS,
+                                 hamiltonian_types=("full",), seed: int = 0x5EED0001,
+                                 engine=None, traj_offset: int = 0, n_shots: int = 1) -> dict:
+    """``get_instances_energy`` as ``BackendEstimatorV2`` forms it: every <P> from
+    the counts of measured bitstrings (``DtcEngine.sample``), the Z-type terms
+    from the Z-basis outcomes and the X-type terms from the X-basis outcomes.
+    With ``n_shots = 1`` every shot is one noisy trajectory and one outcome of
+    it, Aer's per-shot statistics.  The Z and the X outcomes of a trajectory
+    share its noise realisation where the reference runs two circuits: each
+    group's partial sum has the reference's distribution, only the covariance
+    between the two groups' partial sums differs.  Raises NotImplementedError
+    for device-like or bond noise."""
+    refuse_sample(spec, "get_instances_energy_sampled")
+    eng = _engine(engine)
+    bits = eng.sample(spec, n_traj, n_shots=n_shots, bases="zx", seed=seed,
+                      traj_offset=traj_offset)
+    obs = observables_from_samples(bits["z"], bits["x"], spec.L)
+    out = {}
+    for ht in hamiltonian_types:
+        out[ht] = np.stack([
+            energy_from_observables({k: v[i] for k, v in obs.items()}, spec.L, _g0(spec.g),
+                                    spec.hs[i], spec.phis[i], ht)
+            for i in range(spec.n_inst)])
+    return out
+
+
 # ---- the scripts' drivers and output files ---------------------------------------
 
 def energy_folder(L: int, variant: str = "full-ham") -> str:
@@ -191,12 +259,13 @@ def energy_folder(L: int, variant: str = "full-ham") -> str:
 
 
 def energy_csv_name(prefix, state, g, L, inst, randomphi, delta, amplitude, noise, use_noise,
-                    bond_noise_prob=0.0, echo=False):
+                    bond_noise_prob=0.0, echo=False, sampled=False):
     """The scripts' file names; with bond noise (no reference counterpart)
     ``_bond{p}`` before the extension, as ``sweep.autocorr_csv_name``; the echo
-    energy's files (the scripts never saved one) ``_echo``."""
+    energy's files (the scripts never saved one) ``_echo``, the sampled
+    estimator's ``_sampled``."""
     bond = f"_bond{bond_noise_prob}" if bond_noise_prob else ""
-    tail = "_echo" if echo else ""
+    tail = ("_echo" if echo else "") + ("_sampled" if sampled else "")
     return (f"{prefix}_{state}_g{g}_L{L}_inst{inst}_randomphi{randomphi}_delta{delta}"
             f"_amplitude{amplitude}_noise{noise}_usenoise{use_noise}{bond}{tail}.csv")
 
@@ -204,7 +273,7 @@ def energy_csv_name(prefix, state, g, L, inst, randomphi, delta, amplitude, nois
 def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
                initial_state="vacuum", n_traj=ESTIMATOR_SHOTS, seed=0x5EED0001,
                hamiltonian_types=("full",), accumulate=True, engine=None, calibration=None,
-               bond_noise=None, echo=False):
+               bond_noise=None, echo=False, sampled=False):
     """energy.py's main loop (:212-222): for each nprob, ``av_energy / L`` per
     Hamiltonian variant.  Returns ``{(ht, nprob): [T]}``.
 
@@ -218,7 +287,21 @@ def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
     after every RZZ, in every column (SweepSpec.bond_noise).
 
     ``echo=True``: every column is the echo energy (``get_instances_energy``);
-    not with ``calibration`` or bond noise."""
+    not with ``calibration`` or bond noise.
+
+    ``sampled=True``: every column from sampled bitstrings
+    (``get_instances_energy_sampled`` with ``n_traj`` trajectories and one shot per
+    trajectory and basis: with ``n_traj = ESTIMATOR_SHOTS`` every basis has Aer's
+    per-shot statistics, one noisy trajectory and one outcome per shot).  The Z
+    and the X outcomes of a trajectory share its noise realisation, where the
+    reference runs two circuits: that changes only the covariance between the two
+    groups' partial sums, not either group's distribution.  Not with ``echo``,
+    ``calibration`` or bond noise.  The default is the trajectory mean of exact
+    expectations."""
+    if sampled and (echo or calibration is not None):
+        raise NotImplementedError(
+            "run_energy(sampled=True) does not support "
+            + ("the echo" if echo else "device-like noise (a calibration)"))
     eff = accumulated_noise(nprobs) if accumulate else [float(p) for p in nprobs]
     res = {}
     for k, (nprob, p_eff) in enumerate(zip(nprobs, eff)):
@@ -232,8 +315,11 @@ def run_energy(L, g, hs, phis, T, nprobs=(0, 0.001, 0.01, 0.1), use_noise=1,
             spec.device = calibration.device_noise(L)
             readout = calibration.site_readout(L)
             run_seed = seed + 7919 * k
-        per = get_instances_energy(spec, n_traj, hamiltonian_types, run_seed, engine,
-                                   readout=readout, echo=echo)
+        if sampled:
+            per = get_instances_energy_sampled(spec, n_traj, hamiltonian_types, run_seed, engine)
+        else:
+            per = get_instances_energy(spec, n_traj, hamiltonian_types, run_seed, engine,
+                                       readout=readout, echo=echo)
         for ht, v in per.items():
             res[(ht, nprob)] = v.mean(axis=0) / L
     return res

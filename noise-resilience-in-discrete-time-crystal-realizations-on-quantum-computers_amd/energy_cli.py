@@ -21,6 +21,13 @@ the Loschmidt echo state, ``qc_qiskit(..., echo=True)`` of the scripts
 (energy.py:141-153); the file name gains ``_echo`` before ``.csv``, the folder is
 unchanged.  Not with device-like noise or bond noise.
 
+``--sampled 1`` (modes full, ham-comparison, vs-echo): the estimator as
+``BackendEstimatorV2`` runs it -- every expectation value from measured bitstrings,
+one noisy trajectory and one Z-basis and one X-basis outcome per shot
+(``energy.get_instances_energy_sampled``) -- instead of the trajectory mean of exact
+expectations; the file name gains ``_sampled`` before ``.csv``, the folder is
+unchanged.  Not with ``--echo 1``, device-like noise or bond noise.
+
 ``--use_fakebackend`` defaults as in each script (1 for vs-echo and fakebrisbane,
 0 otherwise).  With 1 the noise is device-like noise from ``--device_calibration``
 (FakeBrisbane's own snapshot ships inside qiskit-ibm-runtime and is not available
@@ -63,6 +70,10 @@ def build_parser():
     p.add_argument("--echo", type=int, default=0, choices=[0, 1],
                    help="1 = the energy of the echo state (t inverse periods after the t forward "
                         "ones); modes full, ham-comparison, vs-echo; file names gain _echo")
+    p.add_argument("--sampled", type=int, default=0, choices=[0, 1],
+                   help="1 = expectation values from sampled bitstrings, one trajectory and one "
+                        "outcome per shot and basis (the estimator's shot noise); file names "
+                        "gain _sampled")
     p.add_argument("--use_fakebackend", type=int, default=None,
                    help="default: 1 for --mode vs-echo / fakebrisbane, else 0 (as the scripts)")
     p.add_argument("--device_calibration", type=str, default=None,
@@ -96,6 +107,18 @@ def main(argv=None):
         if args.bond_noise_prob or args.fakebackend_bond:
             raise SystemExit("--echo 1: the energy echo does not support bond noise "
                              "(--bond_noise_prob / --fakebackend_bond)")
+    sampled = bool(args.sampled)
+    if sampled:
+        # refused before anything runs
+        if echo:
+            raise SystemExit("--sampled 1 does not support --echo 1: the echo state is never "
+                             "stored, so it is not sampled")
+        if use_fake or args.mode == "fakebrisbane":
+            raise SystemExit("--sampled 1 does not support device-like noise "
+                             "(--use_fakebackend 1); pass --use_fakebackend 0")
+        if args.bond_noise_prob or args.fakebackend_bond:
+            raise SystemExit("--sampled 1 does not support bond noise "
+                             "(--bond_noise_prob / --fakebackend_bond)")
     cal = None
     if use_fake:
         from .cli import DEFAULT_CALIBRATION
@@ -108,7 +131,7 @@ def main(argv=None):
 
     bond, bond_tag = bond_from_args(args, cal, L)
     tagged = (lambda prefix: en.energy_csv_name(prefix, *name_args, bond_noise_prob=bond_tag,
-                                                echo=echo))
+                                                echo=echo, sampled=sampled))
     if args.mode == "fakebrisbane":
         e = en.run_energy_device(L, args.g, hs, phis, T, cal, initial_state=args.initial_state,
                                  n_traj=args.trajectories, seed=args.seed,
@@ -121,7 +144,7 @@ def main(argv=None):
         noisy = bool(args.use_noise)
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=int(noisy),
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo)
+                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo, sampled=sampled)
         cols = {f"energy_p_{p}": res[("full", p)] for p in nprobs}
         path = os.path.join(args.out_dir, en.energy_folder(L, "full-ham"),
                             tagged("energy_data"))
@@ -129,7 +152,7 @@ def main(argv=None):
         nprobs = [args.noise_prob]
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=1,
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo,
+                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo, sampled=sampled,
                             hamiltonian_types=("z_only", "zz_only", "x_only", "full"))
         cols = {}
         for p in nprobs:
@@ -144,7 +167,7 @@ def main(argv=None):
         nprobs = [0.1]
         res = en.run_energy(L, args.g, hs, phis, T, nprobs, use_noise=1,
                             initial_state=args.initial_state, n_traj=args.trajectories,
-                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo,
+                            seed=args.seed, calibration=cal, bond_noise=bond, echo=echo, sampled=sampled,
                             hamiltonian_types=("full", "z_zz"))
         cols = {}
         for p in nprobs:
@@ -189,6 +212,8 @@ def write_comprehensive(args, ts, e_with, e_without):
         name = "comprehensive_data_energy_only_" + tail
     if args.echo:
         name = name[:-len(".csv")] + "_echo.csv"
+    if args.sampled:
+        name = name[:-len(".csv")] + "_sampled.csv"
     path = os.path.join(args.out_dir, en.energy_folder(L, "ham-comparison"), name)
     os.makedirs(os.path.dirname(path), exist_ok=True)
     pd.DataFrame(data).to_csv(path, index=False)

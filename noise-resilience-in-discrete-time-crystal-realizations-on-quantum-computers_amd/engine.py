@@ -151,6 +151,48 @@ def refuse_energy_echo(spec: SweepSpec, what: str) -> None:
             "diagonal tables and plain chains are not built for the energy echo")
 
 
+def refuse_sample(spec: SweepSpec, what: str) -> None:
+    """Measurement sampling runs depolarizing or noiseless kicks only."""
+    if getattr(spec, "device", None) is not None:
+        raise NotImplementedError(
+            f"{what} does not support device-like noise (SweepSpec.device): a shot of a "
+            "Kraus-weighted trajectory would have to carry the trajectory's norm as a weight")
+    if getattr(spec, "has_bond_noise", False):
+        raise NotImplementedError(
+            f"{what} does not support bond noise (SweepSpec.bond_noise): there is no sampled "
+            "entry point taking its per-state diagonal tables")
+
+
+def sample_draws(seed: int, traj: int, p: int, basis: int, n_shots: int) -> np.ndarray:
+    """Host only (dtc_sample_draws): the uniforms in [0, 1) of the ``n_shots``
+    measurement shots of trajectory ``traj`` after ``p`` periods in ``basis``
+    (0 = Z, 1 = X)."""
+    lib = _capi.load_library()
+    u = np.zeros(int(n_shots))
+    _capi.check(lib.dtc_sample_draws(
+        ctypes.c_uint64(seed), ctypes.c_int64(traj), ctypes.c_int32(p), ctypes.c_int32(basis),
+        ctypes.c_int32(n_shots), _capi.as_dptr(u)))
+    return u
+
+
+def sample_state(psi, L: int, basis: int, u) -> np.ndarray:
+    """Host only (dtc_sample_state), the sampling contract's reference: the
+    outcome of every uniform of ``u`` on the state ``psi`` (2^L amplitudes, site
+    i = bit i): the smallest x whose running sum of ``|psi|^2`` in index order
+    exceeds ``u W``; ``basis`` 1 applies a Hadamard to every site first."""
+    lib = _capi.load_library()
+    buf = np.ascontiguousarray(np.asarray(psi, dtype=np.complex128).reshape(-1))
+    if buf.size != 1 << L:
+        raise ValueError(f"psi must hold 2^L = {1 << L} amplitudes")
+    uu = np.ascontiguousarray(np.atleast_1d(np.asarray(u, dtype=np.float64)))
+    bits = np.zeros(uu.size, dtype=np.uint64)
+    _capi.check(lib.dtc_sample_state(
+        _capi.as_dptr(buf.view(np.float64)), ctypes.c_int32(L), ctypes.c_int32(basis),
+        _capi.as_dptr(uu), ctypes.c_int32(uu.size),
+        bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    return bits
+
+
 def bond_struct(p_bond: np.ndarray) -> "_capi.DtcBondNoise":
     b = _capi.DtcBondNoise()
     b.p_bond = _capi.as_dptr(p_bond)
@@ -503,6 +545,28 @@ class DtcEngine:
         (dtc_energy_sums_bond)."""
         return self._energy_bond(self._lib.dtc_energy_sums_bond, spec, (spec.n_inst,), n_traj,
                                  seed, traj_offset, batch)
+
+    def sample(self, spec: SweepSpec, n_traj: int, n_shots: int = 1, bases: str = "zx",
+               seed: int = 0x5EED0001, traj_offset: int = 0, batch: int = 0, t_first: int = 0):
+        """Measurement outcomes of the forward sweep (dtc_sample): for every
+        trajectory of ``energy`` and every time t, ``n_shots`` bitstrings per
+        requested basis, ``{"z": uint64 [n_inst][n_traj][T][n_shots], "x": ...}``
+        (site i = bit i; in ``x`` a set bit means X_i = -1).  Rows before
+        ``t_first`` stay 0.  Depolarizing or noiseless kicks only."""
+        refuse_sample(spec, "sample")
+        bases = str(bases).lower()
+        if not bases or set(bases) - set("zx"):
+            raise ValueError(f"bases must name 'z', 'x' or both, got {bases!r}")
+        shape = (spec.n_inst, int(n_traj), spec.T, int(n_shots))
+        out = {b: np.zeros(shape, dtype=np.uint64) for b in "zx" if b in bases}
+        up = ctypes.POINTER(ctypes.c_uint64)
+        pr = self._problem(spec, True, False, batch, t_first)
+        _capi.check(self._lib.dtc_sample(
+            self._ctx, ctypes.byref(pr), ctypes.byref(self._noise(spec)), ctypes.c_uint64(seed),
+            ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj), ctypes.c_int32(n_shots),
+            out["z"].ctypes.data_as(up) if "z" in out else None,
+            out["x"].ctypes.data_as(up) if "x" in out else None))
+        return out
 
     # -- sharded state (dtc_shard_*; driver: sharded.py) ----------------
     def shard_set_basis(self, spec: SweepSpec, shard, state_ptr: int, seed: int = 0x5EED0001,
