@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -207,6 +208,30 @@ int settle_pending(dtc_ctx* ctx) {
   return ctx->pending.size() > 16384 ? resolve_pending(ctx) : DTC_OK;
 }
 
+// One launch, bracketed by a pair of events when profiling is on and booked
+// under `kind` with its algorithmic bytes (`what`: the launch's text, for the
+// error message).
+template <class Fn>
+int timed(dtc_ctx* ctx, int kind, double bytes, const char* what, Fn&& launch) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->prof) {
+    e0 = get_event(ctx);
+    e1 = get_event(ctx);
+    DTC_HIP(hipEventRecord(e0, ctx->stream));
+  }
+  const hipError_t e = launch();
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? DTC_ENOMEM : DTC_EHIP,
+                std::string(what) + ": " + hipGetErrorString(e));
+  if (ctx->prof) {
+    DTC_HIP(hipEventRecord(e1, ctx->stream));
+    ctx->pending.push_back(Pending{kind, e0, e1, bytes});
+  }
+  return DTC_OK;
+}
+#define DTC_TIMED(ctx, kind, bytes, expr) \
+  DTC_TRY(timed(ctx, kind, bytes, #expr, [&] { return (expr); }))
+
 // Diagonal factor tables (RZZ even/odd bonds + RZ, fast.py:115-120):
 // D(x) = exp(-i/2 (sum_i h_i z_i + sum_i phi_i z_i z_{i+1})), z_i = 1 - 2 bit_i(x).
 // Per instance: n_chunks chunk tables, D(x) = prod_k C_k[(x >> 5k) & 63] (C_k covers
@@ -300,16 +325,10 @@ dtc::PrepArgs prep_args(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int
 int launch_reduce_prof(dtc_ctx* ctx, int n_tiles, int n_obs, int batch, double* out,
                        int64_t out_stride, int o_first = 0, int n_out = -1,
                        int accumulate = 0) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->prof) {
-    e0 = get_event(ctx);
-    e1 = get_event(ctx);
-    DTC_HIP(hipEventRecord(e0, ctx->stream));
-  }
+  const int no = n_out < 0 ? n_obs - o_first : n_out;
   double* scratch = nullptr;
   if (dtc::reduce_splits(n_tiles) > 1) {
     // split sums of a large state's tiles ([batch][splits][n_out])
-    const int no = n_out < 0 ? n_obs - o_first : n_out;
     const size_t need = (size_t)batch * dtc::reduce_splits(n_tiles) * no * sizeof(double);
     if (ctx->red_scratch.n < need) {
       DTC_HIP(hipStreamSynchronize(ctx->stream));  // the previous scratch may be in use
@@ -317,14 +336,9 @@ int launch_reduce_prof(dtc_ctx* ctx, int n_tiles, int n_obs, int batch, double* 
     }
     scratch = (double*)ctx->red_scratch.p;
   }
-  DTC_HIP(dtc::launch_reduce((const double*)ctx->partial.p, n_tiles, n_obs, batch, out,
-                             out_stride, ctx->stream, o_first, n_out, accumulate, scratch));
-  if (ctx->prof) {
-    DTC_HIP(hipEventRecord(e1, ctx->stream));
-    ctx->pending.push_back(
-        Pending{DTC_KERNEL_REDUCE, e0, e1,
-                8.0 * (double)n_tiles * (n_out < 0 ? n_obs - o_first : n_out) * batch});
-  }
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE, 8.0 * (double)n_tiles * no * batch,
+            dtc::launch_reduce((const double*)ctx->partial.p, n_tiles, n_obs, batch, out,
+                               out_stride, ctx->stream, o_first, n_out, accumulate, scratch));
   return DTC_OK;
 }
 
@@ -446,29 +460,17 @@ int launch_pass_spec(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int ba
     return fail(DTC_EINVAL, "internal: a dual pass is a stored K-D-K / K-D with its branch's records");
   const int kernel = no_store ? DTC_KERNEL_FINAL_PASS
                               : (ps.diag != dtc::kDiagNone ? DTC_KERNEL_LO_PASS : DTC_KERNEL_HI_PASS);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->prof) {
-    e0 = get_event(ctx);
-    e1 = get_event(ctx);
-    DTC_HIP(hipEventRecord(e0, ctx->stream));
-  }
+  // the slice's last pre-exchange kick, stored at the partner piece
+  if (swap_k > 0 && (shape != dtc::kShapeK || meas_mode != dtc::kMeasNone || basis))
+    return fail(DTC_EINVAL, "internal: kick+exchange pass must be a plain kick pass");
+  // algorithmic bytes: a read and a store per amplitude, or one of them
+  // (measure-only passes store nothing, a basis-synthesising pass reads nothing)
+  const double per_amp = (no_store || basis) ? 16.0 : (dst2 ? 48.0 : 32.0);
   int lc_variant = -1;
-  if (swap_k > 0) {
-    // the slice's last pre-exchange kick, stored at the partner piece
-    if (shape != dtc::kShapeK || meas_mode != dtc::kMeasNone || basis)
-      return fail(DTC_EINVAL, "internal: kick+exchange pass must be a plain kick pass");
-    DTC_HIP(dtc::launch_kick_swap(A, swap_k, kind, ctx->stream));
-  } else {
-    DTC_HIP(dtc::launch_pass(A, batch, shape, kind, ctx->stream, &lc_variant));
-  }
+  DTC_TIMED(ctx, kernel, per_amp * (double)((int64_t)1 << A.L_eff) * batch,
+            swap_k > 0 ? dtc::launch_kick_swap(A, swap_k, kind, ctx->stream)
+                       : dtc::launch_pass(A, batch, shape, kind, ctx->stream, &lc_variant));
   if (lc_variant >= 0 && lc_variant < 4) ++ctx->lc_launches[lc_variant];
-  if (ctx->prof) {
-    DTC_HIP(hipEventRecord(e1, ctx->stream));
-    // algorithmic bytes: a read and a store per amplitude, or one of them
-    // (measure-only passes store nothing, a basis-synthesising pass reads nothing)
-    const double per_amp = (no_store || basis) ? 16.0 : (dst2 ? 48.0 : 32.0);
-    ctx->pending.push_back(Pending{kernel, e0, e1, per_amp * (double)((int64_t)1 << A.L_eff) * batch});
-  }
   if (meas_mode != dtc::kMeasNone && meas_out)
     DTC_TRY(launch_reduce_prof(ctx, 1 << (A.L_eff - g.tb), n_obs, batch, meas_out, meas_stride));
   return DTC_OK;
@@ -494,19 +496,9 @@ int launch_wf(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch, co
   A.dmask = l.wf_dmask;
   A.tab = (const double2*)ctx->wf_tab.p + (size_t)l.wf_set * rc.prob->n_inst * kWfSetStride;
   A.out_bit = g.out_bit;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->prof) {
-    e0 = get_event(ctx);
-    e1 = get_event(ctx);
-    DTC_HIP(hipEventRecord(e0, ctx->stream));
-  }
-  DTC_HIP(dtc::launch_wavefront(A, l.wf_kind, ctx->stream));
+  DTC_TIMED(ctx, DTC_KERNEL_LO_PASS, 32.0 * (double)((int64_t)1 << A.L_eff) * batch,
+            dtc::launch_wavefront(A, l.wf_kind, ctx->stream));
   ++ctx->wf_launches;
-  if (ctx->prof) {
-    DTC_HIP(hipEventRecord(e1, ctx->stream));
-    ctx->pending.push_back(Pending{DTC_KERNEL_LO_PASS, e0, e1,
-                                   32.0 * (double)((int64_t)1 << A.L_eff) * batch});
-  }
   return DTC_OK;
 }
 
@@ -534,18 +526,8 @@ int launch_bond_tables(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int 
   B.inverse = l.bond_inv;
   if (ctx->bond_diag.n < (size_t)batch * B.diag_stride * sizeof(double2))
     return fail(DTC_EINVAL, "internal: bond table buffer too small");
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->prof) {
-    e0 = get_event(ctx);
-    e1 = get_event(ctx);
-    DTC_HIP(hipEventRecord(e0, ctx->stream));
-  }
-  DTC_HIP(dtc::launch_bond_diag(B, ctx->stream));
-  if (ctx->prof) {
-    DTC_HIP(hipEventRecord(e1, ctx->stream));
-    ctx->pending.push_back(Pending{DTC_KERNEL_INIT, e0, e1,
-                                   (double)batch * B.diag_stride * sizeof(double2)});
-  }
+  DTC_TIMED(ctx, DTC_KERNEL_INIT, (double)batch * B.diag_stride * sizeof(double2),
+            dtc::launch_bond_diag(B, ctx->stream));
   return DTC_OK;
 }
 
@@ -564,23 +546,36 @@ int launch_bond_signs(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int b
   B.n_traj = rc.n_traj;
   B.traj_offset = rc.traj_offset;
   B.seed = rc.seed;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->prof) {
-    e0 = get_event(ctx);
-    e1 = get_event(ctx);
-    DTC_HIP(hipEventRecord(e0, ctx->stream));
-  }
-  DTC_HIP(dtc::launch_bond_obs_sign(B, ctx->stream));
-  if (ctx->prof) {
-    DTC_HIP(hipEventRecord(e1, ctx->stream));
-    ctx->pending.push_back(
-        Pending{DTC_KERNEL_REDUCE, e0, e1, 16.0 * (double)batch * T * 3 * rc.pl.L});
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE, 16.0 * (double)batch * T * 3 * rc.pl.L,
+            dtc::launch_bond_obs_sign(B, ctx->stream));
+  return DTC_OK;
+}
+
+// E = H^L F: one noiseless basis-change pass per site group, F -> E, then
+// E -> E.  Each pass prepares its own records in ctx->recs1 (launch_pass_spec),
+// so the records of the segment that run_launches is streaming, in ctx->recs,
+// stay in place.  measure_last: the last pass leaves per-site Z of E -- X of F
+// -- in ctx->partial (1 + L values) for the caller's reduce.
+int launch_xbasis(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
+                  const double2* F, double2* E, bool measure_last) {
+  const int G = (int)rc.pl.groups.size(), n_obs = measure_last ? 1 + rc.pl.L : 0;
+  for (int g = 0; g < G; ++g) {
+    PassSpec xs{g, no_kick(), no_kick(), dtc::kDiagNone, 0};
+    xs.pre = dtc::KickDesc{1, 0, dtc::kKickBasisX, 0u, 0u, 0u};
+    DTC_TRY(launch_pass_spec(ctx, rc, batch_start, batch, xs, g == 0 ? F : E, E,
+                             measure_last && g == G - 1 ? dtc::kMeasSites : dtc::kMeasNone,
+                             measure_last ? 1 : 0, n_obs, nullptr, 0));
   }
   return DTC_OK;
 }
 
+// Stream a batch's schedule: the kick records of every pass prepared with one
+// launch per segment, then the passes with their reduces.  `after` (optional):
+// called behind a launch, and its reduces, that leaves the state of a time in
+// its dst (Launch::t_state >= 0).
+using AfterLaunch = std::function<int(const Launch&)>;
 int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
-                 const std::vector<Launch>& L) {
+                 const std::vector<Launch>& L, const AfterLaunch& after = nullptr) {
 #ifdef DTC_DEV_KNOBS
   // development builds: DTC_PRINT_SCHED=1 lists the batch's schedule on stderr
   // (the listing of tools/schedule_check.cpp; F0 there is the prefix here)
@@ -609,6 +604,9 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
   row0[L.size()] = ctx->pk_host.size();
   const size_t n_rows = ctx->pk_host.size();
   const size_t per_pass = (size_t)batch * dtc::kRecPerState * sizeof(dtc::KickRec);
+  // (a pass's records take batch * 27 * 64 B, at most 113 MB at the largest
+  // batch of 65535 states, so 256 MiB / per_pass >= 2 always: the lower bound
+  // only sizes the buffer of a one-row schedule)
   const size_t seg = std::max<size_t>(2, std::min<size_t>(n_rows, (size_t)(256u << 20) / per_pass));
   DTC_TRY(ensure(ctx->recs, seg * per_pass));
   DTC_TRY(ensure(ctx->pk, n_rows * sizeof(dtc::PassKick)));
@@ -636,15 +634,13 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
                                l.meas_parts, l.no_store, l.basis, 0,
                                l.dst2 ? rec + batch * dtc::kRecPerState : nullptr, l.dst2,
                                l.bond_diag ? (const double2*)ctx->bond_diag.p : nullptr));
-      if (l.meas_parts) {
-        // the end's observables into its (zeroed) time row: Z, ZZ of all sites
-        // from the chain's last pass, X of each site from its group's end
-        const int Ls = rc.pl.L;
-        const bool zpart = (l.meas_parts & dtc::kPartZ) != 0;
-        DTC_TRY(launch_reduce_prof(ctx, rc.pl.n_tiles, l.n_obs, batch,
-                                   l.energy_row + (zpart ? 0 : 2 * Ls), l.meas_stride,
-                                   zpart ? 0 : 2 * Ls, zpart ? 3 * Ls : Ls, 1));
-      }
+      // the pass's observables into their (zeroed) time rows (reduce_ranges)
+      ReduceRange rr[2];
+      const int n_rr = reduce_ranges(l, rc.pl.L, rr);
+      for (int k = 0; k < n_rr; ++k)
+        DTC_TRY(launch_reduce_prof(ctx, rc.pl.n_tiles, l.n_obs, batch, rr[k].out, l.meas_stride,
+                                   rr[k].o_first, rr[k].n_out, 1));
+      if (l.t_state >= 0 && after) DTC_TRY(after(l));
     }
     i0 = i1;
   }
@@ -654,8 +650,7 @@ int run_launches(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch,
 // The basis states of a batch (masks already in ctx->basis) as the source of
 // its schedule: a first pass that only kicks forms them in registers (no
 // zero-fill of F, no read of it); any other first pass reads F, filled here.
-template <class LaunchT>
-int basis_source(dtc_ctx* ctx, std::vector<LaunchT>& sched, double2* F, int64_t len, int nb,
+int basis_source(dtc_ctx* ctx, std::vector<Launch>& sched, double2* F, int64_t len, int nb,
                  int octet_bits) {
   if (!sched.empty() && pass_shape(sched[0].ps) == dtc::kShapeK && ctx->basis_synth) {
     sched[0].basis = (const int64_t*)ctx->basis.p;
@@ -1347,6 +1342,51 @@ int auto_batch(dtc_ctx* ctx, double per_state, size_t reusable, bool large_state
   return DTC_OK;
 }
 
+// The batches of a batched run: S states, B per batch (Bp: padded to whole
+// octets), in the state layout `octet` (dtc_kernels.h state_base).
+struct Batch {
+  int64_t S = 0, B = 0, Bp = 0;
+  int octet = 0;
+};
+
+// Size a run's batches and make room for one: the problem's batch size, or the
+// automatic one (auto_batch: states of per_state bytes, `reusable`, the
+// large-state rule), capped at max_B where given (> 0); its layout, into rc
+// too; then F, E (need_E) and the basis masks.  prefix_octet >= 0: the states
+// the run starts from are in place in that layout (dtc_prefix_build), which
+// the batches take over.
+int plan_batch(dtc_ctx* ctx, RunCfg& rc, double per_state, size_t reusable, bool large_state_rule,
+               int64_t max_B, bool need_E, int prefix_octet, Batch& bt) {
+  bt.S = (int64_t)rc.prob->n_inst * rc.n_traj;
+  bt.B = rc.prob->batch;
+  if (bt.B <= 0) DTC_TRY(auto_batch(ctx, per_state, reusable, large_state_rule, bt.B));
+  if (max_B > 0) bt.B = std::max<int64_t>(1, std::min<int64_t>(bt.B, max_B));
+  batch_layout(ctx, rc.pl.L_eff, bt.S, bt.B, bt.octet);
+  if (prefix_octet >= 0) {
+    bt.octet = prefix_octet;
+    if (bt.octet && bt.B < bt.S) {
+      bt.B &= ~(int64_t)7;
+      if (bt.B < 8) return fail(DTC_EINVAL, "batch too small for the prefix's octet layout");
+    }
+  }
+  rc.octet_bits = bt.octet;
+  bt.Bp = dtc::octet_padded(bt.B, bt.octet);
+  DTC_TRY(ensure(ctx->F, (size_t)(bt.Bp * rc.pl.len * 16)));
+  if (need_E) DTC_TRY(ensure(ctx->E, (size_t)(bt.Bp * rc.pl.len * 16)));
+  DTC_TRY(ensure(ctx->basis, (size_t)bt.B * sizeof(int64_t)));
+  return DTC_OK;
+}
+
+// The initial basis states of batch [bs, bs + nb): their masks, and the upload
+// to ctx->basis.
+int batch_masks(dtc_ctx* ctx, const RunCfg& rc, int64_t bs, int nb, std::vector<int64_t>& masks) {
+  for (int b = 0; b < nb; ++b)
+    masks[b] = (int64_t)init_state_mask(rc, (uint64_t)(rc.traj_offset + (bs + b) % rc.n_traj));
+  DTC_HIP(hipMemcpyAsync(ctx->basis.p, masks.data(), nb * sizeof(int64_t), hipMemcpyHostToDevice,
+                         ctx->stream));
+  return DTC_OK;
+}
+
 // What a prefixed run needs of the prefix in place (dtc_prefix_build).
 int check_prefix(const dtc_ctx* ctx, const dtc_problem* pr, const RunCfg& rc, int64_t S,
                  bool device) {
@@ -1478,20 +1518,12 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   // continuation of a prefix: periods 1..n_pre come from dtc_prefix_build
   if (use_prefix) DTC_TRY(check_prefix(ctx, pr, rc, S, dv != nullptr));
   const double per_state = (double)pl.len * 16.0 * (want_e ? 2.0 : 1.0);
-  int64_t B = pr->batch;
-  if (B <= 0) DTC_TRY(auto_batch(ctx, per_state, ctx->F.n + ctx->E.n, true, B));
-  int octet = 0;
-  batch_layout(ctx, rc.pl.L_eff, S, B, octet);
-  if (use_prefix) {
-    // the prefix's states are in the layout they were built in
-    octet = ctx->prefix_octet;
-    if (octet && B < S) {
-      B &= ~(int64_t)7;
-      if (B < 8) return fail(DTC_EINVAL, "batch too small for the prefix's octet layout");
-    }
-  }
-  rc.octet_bits = octet;
-  const int64_t Bp = dtc::octet_padded(B, octet);
+  // (the prefix's states are in the layout they were built in)
+  Batch bt;
+  DTC_TRY(plan_batch(ctx, rc, per_state, ctx->F.n + ctx->E.n, true, 0, want_e,
+                     use_prefix ? ctx->prefix_octet : -1, bt));
+  const int64_t B = bt.B;
+  const int octet = bt.octet;
   if (ctx->verbose) {
     size_t fr = 0, to = 0;
     (void)hipMemGetInfo(&fr, &to);
@@ -1500,8 +1532,6 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                  to / 1073741824.0);
   }
 
-  DTC_TRY(ensure(ctx->F, (size_t)(Bp * pl.len * 16)));
-  if (want_e) DTC_TRY(ensure(ctx->E, (size_t)(Bp * pl.len * 16)));
   const int max_obs = std::max(n_obs_f, n_obs_e);
   DTC_TRY(ensure(ctx->partial, (size_t)B * pl.n_tiles * max_obs * sizeof(double)));
   DTC_TRY(ensure(ctx->vals_f, (size_t)B * T * n_obs_f * sizeof(double)));
@@ -1516,7 +1546,6 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     std::fill(ee->x, ee->x + n_out * L, 0.0);
     if (L > 1) std::fill(ee->zz, ee->zz + n_out * (L - 1), 0.0);
   }
-  DTC_TRY(ensure(ctx->basis, (size_t)B * sizeof(int64_t)));
   if (rc.bond) DTC_TRY(ensure(ctx->bond_diag, (size_t)B * pl.diag_stride * sizeof(double2)));
 
   DTC_TRY(ensure_host(ctx->host_f, (size_t)B * T * n_obs_f));
@@ -1532,11 +1561,10 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
 
   for (int64_t bs = 0; bs < S; bs += B) {
     const int nb = (int)std::min<int64_t>(B, S - bs);
-    for (int b = 0; b < nb; ++b) {
-      const int64_t g = bs + b;
-      masks[b] = use_prefix ? ctx->prefix_masks[g]
-                            : (int64_t)init_state_mask(rc, (uint64_t)(traj_offset + g % n_traj));
-    }
+    if (use_prefix)
+      std::copy_n(ctx->prefix_masks.begin() + bs, nb, masks.begin());
+    else
+      DTC_TRY(batch_masks(ctx, rc, bs, nb, masks));
     double2* F = (double2*)ctx->F.p;
     double2* E = (double2*)ctx->E.p;
 #ifdef DTC_DEV_KNOBS
@@ -1547,10 +1575,6 @@ int autocorr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     // the first forward pass reads the prefix states (or the basis states in F)
     // (bs is a multiple of 8 in the octet layout: the batch starts an octet)
     const double2* F0 = use_prefix ? (const double2*)ctx->prefix.p + (size_t)bs * pl.len : F;
-    if (!use_prefix) {
-      DTC_HIP(hipMemcpyAsync(ctx->basis.p, masks.data(), nb * sizeof(int64_t),
-                             hipMemcpyHostToDevice, ctx->stream));
-    }
     DTC_HIP(hipMemsetAsync(ctx->vals_f.p, 0, (size_t)nb * T * n_obs_f * sizeof(double),
                            ctx->stream));
     if (want_e)
@@ -1620,11 +1644,7 @@ int prefix_build_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
     double2* F = (double2*)ctx->prefix.p + (size_t)bs * pl.len;
     DTC_HIP(hipMemcpyAsync(ctx->basis.p, ctx->prefix_masks.data() + bs, nb * sizeof(int64_t),
                            hipMemcpyHostToDevice, ctx->stream));
-    Chain fw = forward_chain(pl, 1, n_periods, dtc::kStreamForward);
-    fw.post_after_d = !rc.device;
-    std::vector<Launch> sched;
-    while (!fw.done())
-      sched.push_back(Launch{next_pass(fw), F, F, dtc::kMeasNone, 0, 2, nullptr, 0});
+    std::vector<Launch> sched = build_prefix_schedule(rc, n_periods, F);
     DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, octet));
     DTC_TRY(run_launches(ctx, rc, bs, nb, sched));
     DTC_HIP(hipStreamSynchronize(ctx->stream));  // the staged pass list is reused
@@ -1839,28 +1859,19 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   DTC_TRY(init_run_cfg(ctx, pr, nz, dv, bond, seed, traj_offset, n_traj, false, rc));
   const Plan& pl = rc.pl;
   const int T = pr->T, L = pr->L;
-  const int P = T - 1 + pr->t_offset;
   const int n_v = 3 * L;    // per time: norm, Z_i, Z_i Z_i+1, X_i
   const int n_obs = 4 * L;  // per pass: the above (mid-pass) + X_i before the pre-kick
   if (n_obs > dtc::kThreads) return fail(DTC_EINVAL, "dtc_energy: L > 64");
   DTC_TRY(upload_tables(ctx, pr, pl));
 
-  const int64_t S = (int64_t)pr->n_inst * n_traj;
-  const double per_state = (double)pl.len * 16.0;
-  int64_t B = pr->batch;
   // (device-like noise: E too, for the X-basis passes)
-  if (B <= 0)
-    DTC_TRY(auto_batch(ctx, dv ? 2 * per_state : per_state, ctx->F.n + (dv ? ctx->E.n : 0), false,
-                       B));
-  int octet = 0;
-  batch_layout(ctx, rc.pl.L_eff, S, B, octet);
-  rc.octet_bits = octet;
-  const int64_t Bp = dtc::octet_padded(B, octet);
-  DTC_TRY(ensure(ctx->F, (size_t)(Bp * pl.len * 16)));
-  if (dv) DTC_TRY(ensure(ctx->E, (size_t)(Bp * pl.len * 16)));
+  const double per_state = (double)pl.len * 16.0 * (dv ? 2.0 : 1.0);
+  Batch bt;
+  DTC_TRY(plan_batch(ctx, rc, per_state, ctx->F.n + (dv ? ctx->E.n : 0), false, 0, dv != nullptr,
+                     -1, bt));
+  const int64_t S = bt.S, B = bt.B;
   DTC_TRY(ensure(ctx->partial, (size_t)B * pl.n_tiles * n_obs * sizeof(double)));
   DTC_TRY(ensure(ctx->vals_f, (size_t)B * T * n_v * sizeof(double)));
-  DTC_TRY(ensure(ctx->basis, (size_t)B * sizeof(int64_t)));
   if (rc.bond) DTC_TRY(ensure(ctx->bond_diag, (size_t)B * pl.diag_stride * sizeof(double2)));
   // per-instance sums: at most (B - 1) / n_traj + 2 instances per batch
   const int64_t max_inst_b = std::min<int64_t>(pr->n_inst, (B - 1) / n_traj + 2);
@@ -1875,163 +1886,25 @@ int energy_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   double* const hv_f = ctx->host_f.p;
   std::vector<int64_t> masks(B);
 
-  // The schedule: the forward chain one kick layer past the last period
-  // (X_P, no D after it), every pass measuring in flight (meas_parts):
-  //  * a pass closing period p: Z, ZZ after the diagonal and X of its sites
-  //    before their post-kick X_p -> time p - t_offset;
-  //  * a pass whose pre-kick is X_nd (nd diagonals applied): X of its sites
-  //    before that kick -> time nd - t_offset, unless its sites' X at that
-  //    time is already taken (one group: the post-kick of the previous pass).
-  // Each group's X at a time is taken exactly once (checked below); the
-  // reduce accumulates the X ranges into the zeroed per-time rows.
-  //
-  // Device-like noise: a non-unitary kick on one site changes <X> of the
-  // others, so nothing is measured across a kick.  The chain starts no layer
-  // in a pass that applies D (2 passes per period); after the pass closing
-  // period p the state is exactly the state at p: Z, ZZ mid-pass, then X by
-  // one noiseless basis-change pass per site group (E = H^L F).
-  //
-  // Bond noise (dtc_energy_bond): every pass that applies D takes the per-state
-  // tables of forward layer d_index, and every kick layer after the first the
-  // outgoing Pauli of the layer before it.  All of the above is measured on
-  // the state before the outgoing Pauli P_t of layer t + t_offset -- mid-pass
-  // after D, before the post-kick or the next pass's pre-kick that absorbs
-  // P_t, and on the X-basis rotation of that same state -- so one sign pass
-  // over the finished rows (launch_bond_obs_sign) applies P_t to all of them.
-  auto tag_bond = [&](Chain& fw) {
-    if (!rc.bond) return;
-    for (size_t k = 1; k < fw.X.size(); ++k) {
-      fw.X[k].bond_on = 1u;
-      fw.X[k].bond_stream = dtc::kStreamForward;
-      fw.X[k].bond_counter = (uint32_t)k;
-    }
-  };
-  struct EPass {
-    PassSpec ps;
-    int parts, t_mid, t_pre;
-    bool xbasis;
-    const int64_t* basis = nullptr;
-    int no_store = 0;
-  };
-  std::vector<EPass> sched;
-  if (P > 0 && dv) {
-    Chain fw = forward_chain(pl, 1, P, dtc::kStreamForward);
-    fw.post_after_d = false;
-    tag_bond(fw);
-    while (!fw.done()) {
-      EPass e{next_pass(fw), 0, -1, -1, false};
-      if (e.ps.diag != dtc::kDiagNone) {
-        const int t = e.ps.d_index - pr->t_offset;
-        if (t >= 0 && t < T) {
-          e.parts = dtc::kPartZ;
-          e.t_mid = t;
-          e.xbasis = true;
-        }
-      }
-      sched.push_back(e);
-    }
-  } else if (P > 0) {
-    const int G = (int)pl.groups.size();
-    Chain fw = forward_chain(pl, 1, P + 1, dtc::kStreamForward);
-    fw.trailing_d = false;
-    fw.X[P].row = P - 1;  // never observed: any valid table row
-    tag_bond(fw);
-    std::vector<char> x_done((size_t)T * G, 0);
-    while (!fw.done()) {
-      const int nd = fw.nd;
-      EPass e{next_pass(fw), 0, -1, -1, false};
-      const int g = e.ps.group;
-      if (e.ps.diag != dtc::kDiagNone) {
-        const int t = e.ps.d_index - pr->t_offset;
-        if (t >= 0 && t < T) {
-          e.parts |= dtc::kPartZ;
-          e.t_mid = t;
-          if (e.ps.post.enabled) {
-            e.parts |= dtc::kPartXPost;
-            x_done[(size_t)t * G + g] = 1;
-          }
-        }
-      }
-      const int te = nd - pr->t_offset;
-      if (e.ps.pre.enabled && nd >= 1 && te >= 0 && te < T && !x_done[(size_t)te * G + g]) {
-        e.parts |= dtc::kPartXPre;
-        e.t_pre = te;
-        x_done[(size_t)te * G + g] = 1;
-      }
-      sched.push_back(e);
-    }
-    for (int t = 0; t < T; ++t)
-      for (int g = 0; g < G; ++g)
-        if (t + pr->t_offset >= 1 && !x_done[(size_t)t * G + g])
-          return fail(DTC_EINVAL, "internal: dtc_energy left an X group unmeasured");
-    // the extra kick layer's pass only measures X: its state is never read
-    if (sched.size() >= 2 && pass_shape(sched.back().ps) == dtc::kShapeK &&
-        (sched.back().parts & dtc::kPartXPre) && !(sched.back().parts & dtc::kPartZ))
-      sched.back().no_store = 1;
-  }
+  // the schedule (build_energy_schedule, dtc_schedule.h) is the same for every
+  // batch; under device-like noise the pass that leaves the state at a time is
+  // followed by that state's X: E = H^L F, per-site Z of E into the row's X part
+  double2* const F = (double2*)ctx->F.p;
+  double* const vals = (double*)ctx->vals_f.p;
+  std::vector<Launch> sched;
+  if (const char* err = build_energy_schedule(rc, F, vals, sched)) return fail(DTC_EINVAL, err);
+  const int64_t vs = (int64_t)T * n_v;
 
   for (int64_t bs = 0; bs < S; bs += B) {
     const int nb = (int)std::min<int64_t>(B, S - bs);
-    for (int b = 0; b < nb; ++b)
-      masks[b] = (int64_t)init_state_mask(rc, (uint64_t)(traj_offset + (bs + b) % n_traj));
-    double2* F = (double2*)ctx->F.p;
-    double* vals = (double*)ctx->vals_f.p;
-    DTC_HIP(hipMemcpyAsync(ctx->basis.p, masks.data(), nb * sizeof(int64_t),
-                           hipMemcpyHostToDevice, ctx->stream));
-    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, octet));
+    DTC_TRY(batch_masks(ctx, rc, bs, nb, masks));
+    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, bt.octet));
     DTC_HIP(hipMemsetAsync(vals, 0, (size_t)nb * T * n_v * sizeof(double), ctx->stream));
-    const int64_t vs = (int64_t)T * n_v;
-    // kick records of the schedule's passes: one prep launch per segment
-    // (the X-basis passes of the device path build their own)
-    const size_t per_pass = (size_t)nb * dtc::kRecPerState * sizeof(dtc::KickRec);
-    const size_t seg = std::max<size_t>(1, std::min<size_t>(sched.size(), (size_t)(256u << 20) / per_pass));
-    DTC_TRY(ensure(ctx->recs, seg * per_pass));
-    ctx->pk_host.resize(sched.size());
-    for (size_t i = 0; i < sched.size(); ++i) ctx->pk_host[i] = pass_kick(rc, sched[i].ps);
-    DTC_TRY(ensure(ctx->pk, sched.size() * sizeof(dtc::PassKick)));
-    DTC_HIP(hipMemcpyAsync(ctx->pk.p, ctx->pk_host.data(), sched.size() * sizeof(dtc::PassKick),
-                           hipMemcpyHostToDevice, ctx->stream));
-    for (size_t i = 0; i < sched.size(); ++i) {
-      const EPass& e = sched[i];
-      if (i % seg == 0) {
-        dtc::PrepArgs Pp = prep_args(ctx, rc, bs, nb);
-        Pp.passes = (const dtc::PassKick*)ctx->pk.p + i;
-        Pp.n_pass = (int)std::min(seg, sched.size() - i);
-        Pp.out = (dtc::KickRec*)ctx->recs.p;
-        DTC_HIP(dtc::launch_prep(Pp, ctx->stream));
-      }
-      const dtc::KickRec* recs = (const dtc::KickRec*)ctx->recs.p + (i % seg) * nb * dtc::kRecPerState;
-      const bool noisy_d = rc.bond && e.ps.diag != dtc::kDiagNone;
-      if (noisy_d) {
-        Launch l{};
-        l.bond_stream = dtc::kStreamForward;
-        l.bond_counter = (uint32_t)e.ps.d_index;
-        DTC_TRY(launch_bond_tables(ctx, rc, bs, nb, l));
-      }
-      DTC_TRY(launch_pass_spec(ctx, rc, bs, nb, e.ps, F, F,
-                               e.parts ? dtc::kMeasEnergy : dtc::kMeasNone, 0, n_obs, nullptr,
-                               0, recs, e.parts, e.no_store, e.basis, 0, nullptr, nullptr,
-                               noisy_d ? (const double2*)ctx->bond_diag.p : nullptr));
-      if (e.parts & dtc::kPartZ)
-        DTC_TRY(launch_reduce_prof(ctx, pl.n_tiles, n_obs, nb, vals + (size_t)e.t_mid * n_v, vs,
-                                   0, (e.parts & dtc::kPartXPost) ? 3 * L : 2 * L, 1));
-      if (e.parts & dtc::kPartXPre)
-        DTC_TRY(launch_reduce_prof(ctx, pl.n_tiles, n_obs, nb,
-                                   vals + (size_t)e.t_pre * n_v + 2 * L, vs, 3 * L, L, 1));
-      if (e.xbasis) {
-        double2* E = (double2*)ctx->E.p;
-        const int G = (int)pl.groups.size();
-        for (int g = 0; g < G; ++g) {
-          PassSpec xs{g, no_kick(), no_kick(), dtc::kDiagNone, 0};
-          xs.pre = dtc::KickDesc{1, 0, dtc::kKickBasisX, 0u, 0u, 0u};
-          const bool last = g == G - 1;
-          DTC_TRY(launch_pass_spec(ctx, rc, bs, nb, xs, g == 0 ? F : E, E,
-                                   last ? dtc::kMeasSites : dtc::kMeasNone, 1, 1 + L, nullptr, 0));
-        }
-        DTC_TRY(launch_reduce_prof(ctx, pl.n_tiles, 1 + L, nb,
-                                   vals + (size_t)e.t_mid * n_v + 2 * L, vs, 1, L, 1));
-      }
-    }
+    const AfterLaunch x_row = [&](const Launch& l) -> int {
+      DTC_TRY(launch_xbasis(ctx, rc, bs, nb, F, (double2*)ctx->E.p, true));
+      return launch_reduce_prof(ctx, pl.n_tiles, 1 + L, nb, l.energy_row + 2 * L, vs, 1, L, 1);
+    };
+    DTC_TRY(run_launches(ctx, rc, bs, nb, sched, x_row));
     if (rc.bond) DTC_TRY(launch_bond_signs(ctx, rc, bs, nb, vals, T));
     if (sums) {
       // the batch's rows summed per instance on the device (the rows of the
@@ -2157,22 +2030,11 @@ int launch_sample(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int batch
   A.seed = rc.seed;
   A.period = (uint32_t)(t + rc.prob->t_offset);
   A.basis = basis;
-  for (int k = 0; k < 2; ++k) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->prof) {
-      e0 = get_event(ctx);
-      e1 = get_event(ctx);
-      DTC_HIP(hipEventRecord(e0, ctx->stream));
-    }
-    DTC_HIP(k == 0 ? dtc::launch_sample_weights(A, ctx->stream)
-                   : dtc::launch_sample_pick(A, ctx->stream));
-    if (ctx->prof) {
-      DTC_HIP(hipEventRecord(e1, ctx->stream));
-      const double bytes = k == 0 ? 16.0 * (double)rc.pl.len * batch
-                                  : (double)batch * n_shots * (8.0 * rc.pl.n_tiles + 16.0 * dtc::kTile);
-      ctx->pending.push_back(Pending{DTC_KERNEL_REDUCE, e0, e1, bytes});
-    }
-  }
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE, 16.0 * (double)rc.pl.len * batch,
+            dtc::launch_sample_weights(A, ctx->stream));
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE,
+            (double)batch * n_shots * (8.0 * rc.pl.n_tiles + 16.0 * dtc::kTile),
+            dtc::launch_sample_pick(A, ctx->stream));
   return DTC_OK;
 }
 
@@ -2213,73 +2075,37 @@ int dtc_sample(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_
   if (P == 0) return DTC_OK;
   DTC_TRY(upload_tables(ctx, pr, pl));
 
-  const double per_state = (double)pl.len * 16.0 * (xbits ? 2.0 : 1.0);
-  int64_t B = pr->batch;
-  if (B <= 0) DTC_TRY(auto_batch(ctx, per_state, ctx->F.n + (xbits ? ctx->E.n : 0), false, B));
   // (the outcomes of a batch: at most 1 GiB)
-  B = std::max<int64_t>(1, std::min<int64_t>(B, (int64_t)((size_t)(1u << 27) / row / 2)));
-  int octet = 0;
-  batch_layout(ctx, pl.L_eff, S, B, octet);
-  rc.octet_bits = octet;
-  const int64_t Bp = dtc::octet_padded(B, octet);
-  DTC_TRY(ensure(ctx->F, (size_t)(Bp * pl.len * 16)));
-  if (xbits) DTC_TRY(ensure(ctx->E, (size_t)(Bp * pl.len * 16)));
-  DTC_TRY(ensure(ctx->basis, (size_t)B * sizeof(int64_t)));
+  const double per_state = (double)pl.len * 16.0 * (xbits ? 2.0 : 1.0);
+  Batch bt;
+  DTC_TRY(plan_batch(ctx, rc, per_state, ctx->F.n + (xbits ? ctx->E.n : 0), false,
+                     std::max<int64_t>(1, (int64_t)((size_t)(1u << 27) / row / 2)), xbits != nullptr,
+                     -1, bt));
+  const int64_t B = bt.B;
   DTC_TRY(ensure(ctx->sample_w, (size_t)B * pl.n_tiles * sizeof(double)));
   DTC_TRY(ensure(ctx->sample_bits, 2 * (size_t)B * row * sizeof(uint64_t)));
   std::vector<int64_t> masks(B);
 
-  // The schedule: the forward chain in K-D passes (post_after_d = false: no
-  // pass that applies D starts the next kick layer), so after the pass closing
-  // period p the state in F is exactly the state at p, as energy_impl keeps it
-  // under device-like noise -- here with the unitary kick kinds.
-  struct SPass {
-    PassSpec ps;
-    int t;  // the time this pass completes (sampled after it), or -1
-    const int64_t* basis = nullptr;
-  };
-  std::vector<SPass> sched;
-  {
-    Chain fw = forward_chain(pl, 1, P, dtc::kStreamForward);
-    fw.post_after_d = false;
-    while (!fw.done()) {
-      SPass e{next_pass(fw), -1};
-      if (e.ps.diag != dtc::kDiagNone) {
-        const int t = e.ps.d_index - pr->t_offset;
-        if (t >= pr->t_first && t < T) e.t = t;
-      }
-      sched.push_back(e);
-    }
-  }
+  // the schedule (build_sample_schedule, dtc_schedule.h) is the same for every
+  // batch; the state a pass leaves at a time is sampled in Z from F, in X from
+  // E = H^L F
+  double2* const F = (double2*)ctx->F.p;
+  uint64_t* const zb = (uint64_t*)ctx->sample_bits.p;
+  uint64_t* const xb = zb + (size_t)B * row;
+  std::vector<Launch> sched = build_sample_schedule(rc, F);
 
   for (int64_t bs = 0; bs < S; bs += B) {
     const int nb = (int)std::min<int64_t>(B, S - bs);
-    for (int b = 0; b < nb; ++b)
-      masks[b] = (int64_t)init_state_mask(rc, (uint64_t)(traj_offset + (bs + b) % n_traj));
-    double2* F = (double2*)ctx->F.p;
-    double2* E = (double2*)ctx->E.p;
-    uint64_t* zb = (uint64_t*)ctx->sample_bits.p;
-    uint64_t* xb = zb + (size_t)B * row;
-    DTC_HIP(hipMemcpyAsync(ctx->basis.p, masks.data(), nb * sizeof(int64_t),
-                           hipMemcpyHostToDevice, ctx->stream));
-    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, octet));
-    for (const SPass& e : sched) {
-      DTC_TRY(launch_pass_spec(ctx, rc, bs, nb, e.ps, F, F, dtc::kMeasNone, 0, 0, nullptr, 0,
-                               nullptr, 0, 0, e.basis));
-      if (e.t < 0) continue;
-      if (zbits) DTC_TRY(launch_sample(ctx, rc, bs, nb, F, e.t, 0u, n_shots, zb));
-      if (xbits) {
-        // E = H^L F: one noiseless basis-change pass per site group
-        const int G = (int)pl.groups.size();
-        for (int g = 0; g < G; ++g) {
-          PassSpec xs{g, no_kick(), no_kick(), dtc::kDiagNone, 0};
-          xs.pre = dtc::KickDesc{1, 0, dtc::kKickBasisX, 0u, 0u, 0u};
-          DTC_TRY(launch_pass_spec(ctx, rc, bs, nb, xs, g == 0 ? F : E, E, dtc::kMeasNone, 0, 0,
-                                   nullptr, 0));
-        }
-        DTC_TRY(launch_sample(ctx, rc, bs, nb, E, e.t, 1u, n_shots, xb));
-      }
-    }
+    DTC_TRY(batch_masks(ctx, rc, bs, nb, masks));
+    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, bt.octet));
+    const AfterLaunch sample = [&](const Launch& l) -> int {
+      if (zbits) DTC_TRY(launch_sample(ctx, rc, bs, nb, F, l.t_state, 0u, n_shots, zb));
+      if (!xbits) return DTC_OK;
+      double2* E = (double2*)ctx->E.p;
+      DTC_TRY(launch_xbasis(ctx, rc, bs, nb, F, E, false));
+      return launch_sample(ctx, rc, bs, nb, E, l.t_state, 1u, n_shots, xb);
+    };
+    DTC_TRY(run_launches(ctx, rc, bs, nb, sched, sample));
     // rows the device did not write (t < t_first, and p = 0, formed above) are
     // kept: only the sampled rows are copied out
     const int t0 = std::max(pr->t_first, pr->t_offset == 0 ? 1 : 0);

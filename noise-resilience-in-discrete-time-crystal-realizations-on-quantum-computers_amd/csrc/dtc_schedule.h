@@ -1,7 +1,9 @@
 // dtc_schedule.h — the device-free schedule of the engine (dtc_engine.cpp):
-// site-group plans, layer chains, passes, and the builder of a batch's launch
-// list (build_autocorr_schedule) with its steps -- the light-cone ends, the
-// dual fold, the wavefront interior.  Everything here computes with integers
+// site-group plans, layer chains, passes, and the builders of a batch's launch
+// list -- the autocorrelator's (build_autocorr_schedule) with its steps, the
+// light-cone ends, the dual fold, the wavefront interior, and the forward
+// sweeps' (build_energy_schedule, build_sample_schedule,
+// build_prefix_schedule).  Everything here computes with integers
 // and opaque buffer addresses: no HIP call, no engine context, so a plain host
 // compiler builds it (tools/schedule_check.cpp dumps the schedules it makes,
 // tests/test_schedule_cpu.py pins them).  The engine owns the context, the
@@ -348,7 +350,38 @@ struct Launch {
   // pass, kPartZ at the end of the pass into the row's first 2 L values
   int meas_parts = 0;
   double* energy_row = nullptr;
+  // a pass of the forward energy sweep (build_energy_schedule; n_obs = 4 L):
+  // kPartZ / kPartXPost go into energy_row, the row of the time the pass's
+  // diagonal closes; kPartXPre -- X of the pass's sites at its entry -- into
+  // energy_row_pre + 2 L, the row of the time before
+  double* energy_row_pre = nullptr;
+  // >= 0: after this launch dst holds exactly the state at time t_state (the
+  // closing pass of a period in a K-D chain, kd_forward_launches); run_launches
+  // then calls the sweep's callback (X-basis rows, sampling)
+  int t_state = -1;
 };
+
+// The ranges of a measured launch's observables that go into its time rows,
+// each accumulated: values [o_first, o_first + n_out) of the pass into out[0 ..
+// n_out).  An end of an energy echo chain: the whole row with Z, else its X
+// part.  A forward pass: Z, ZZ (with the X taken before the post-kick) into the
+// row of its diagonal, the entry X into the row before.
+struct ReduceRange {
+  double* out;
+  int o_first, n_out;
+};
+inline int reduce_ranges(const Launch& l, int L, ReduceRange out[2]) {
+  const int p = l.meas_parts;
+  int n = 0;
+  if (p & dtc::kPartXEnd) {
+    out[n++] = (p & dtc::kPartZ) ? ReduceRange{l.energy_row, 0, 3 * L}
+                                 : ReduceRange{l.energy_row + 2 * L, 2 * L, L};
+    return n;
+  }
+  if (p & dtc::kPartZ) out[n++] = ReduceRange{l.energy_row, 0, (p & dtc::kPartXPost) ? 3 * L : 2 * L};
+  if (p & dtc::kPartXPre) out[n++] = ReduceRange{l.energy_row_pre + 2 * L, 3 * L, L};
+  return n;
+}
 
 // The tile geometry of the wavefront tiles (WfArgs / PassKick c, s, act) and
 // the index bit outside the tile that one of its bonds reaches.
@@ -899,6 +932,26 @@ inline bool wavefront_applies(const RunCfg& rc, const SchedOpts& so, const Sched
   return wf_on;
 }
 
+// Bond noise: period q's kicks take the outgoing Pauli of layer q - 1 (fw: a
+// forward chain whose layer 0 is period `first`'s).
+inline void tag_bond(const RunCfg& rc, Chain& fw, int first) {
+  if (!rc.bond) return;
+  for (size_t k = 1; k < fw.X.size(); ++k) {
+    fw.X[k].bond_on = 1u;
+    fw.X[k].bond_stream = dtc::kStreamForward;
+    fw.X[k].bond_counter = (uint32_t)(first - 1 + k);
+  }
+}
+
+// ... and a forward pass that applies D takes the per-state tables of the
+// noisy layer of period p.
+inline void tag_bond_diag(const RunCfg& rc, Launch& l, int p) {
+  if (!rc.bond || l.ps.diag == dtc::kDiagNone) return;
+  l.bond_diag = 1;
+  l.bond_stream = dtc::kStreamForward;
+  l.bond_counter = (uint32_t)p;
+}
+
 // The sweep's forward chain K_{n_pre+1} D ... K_P D, with its bond tags and the
 // order of its groups.
 inline Chain sweep_forward_chain(const SchedBuild& b) {
@@ -908,13 +961,7 @@ inline Chain sweep_forward_chain(const SchedBuild& b) {
   const int n_pre = b.rq.n_pre, P = pr->T - 1 + pr->t_offset;
   Chain fw = forward_chain(pl, n_pre + 1, P - n_pre, dtc::kStreamForward);
   fw.post_after_d = !b.dev_kd();
-  // bond noise: period q's kicks take the outgoing Pauli of layer q - 1
-  if (rc.bond)
-    for (size_t k = 1; k < fw.X.size(); ++k) {
-      fw.X[k].bond_on = 1u;
-      fw.X[k].bond_stream = dtc::kStreamForward;
-      fw.X[k].bond_counter = (uint32_t)(n_pre + k);
-    }
+  tag_bond(rc, fw, n_pre + 1);
   // start on a group without the probe site: every echo chain then ends
   // with its kick-only pass on such a group, which the probe does not need
   // (two groups: the closing groups alternate with p, see below)
@@ -938,11 +985,7 @@ inline Launch forward_launch(const SchedBuild& b, const PassSpec& ps, int p, int
   Launch l{ps, b.sched.empty() ? b.bufs.F0 : b.bufs.F, b.bufs.F,
            meas ? b.rq.meas_f : dtc::kMeasNone, 0, n_obs_f,
            meas ? b.bufs.vals_f + (size_t)t * n_obs_f : nullptr, (int64_t)pr->T * n_obs_f};
-  if (rc.bond && closes) {
-    l.bond_diag = 1;
-    l.bond_stream = dtc::kStreamForward;
-    l.bond_counter = (uint32_t)p;
-  }
+  tag_bond_diag(rc, l, p);
   return l;
 }
 
@@ -1243,6 +1286,142 @@ inline const char* build_autocorr_schedule(const RunCfg& rc, const SchedOpts& so
   return nullptr;
 }
 
+// ---- the forward sweeps: energy, sampling, the prefix ------------------------
+// The launches F -> F of a forward chain from period 1, nothing measured.
+inline std::vector<Launch> chain_launches(const RunCfg& rc, Chain fw, double2* F, int n_obs,
+                                          int64_t meas_stride) {
+  std::vector<Launch> sched;
+  while (!fw.done()) {
+    Launch l{next_pass(fw), F, F, dtc::kMeasNone, 0, n_obs, nullptr, meas_stride};
+    tag_bond_diag(rc, l, l.ps.d_index);
+    sched.push_back(l);
+  }
+  return sched;
+}
+
+// The whole forward chain K_1 D ... K_P D in K-D passes (post_after_d = false:
+// no pass that applies D starts the next kick layer), so after the pass closing
+// period p the state in F is exactly the state at t = p - t_offset: t_state
+// there, for t_lo <= t < T.
+inline std::vector<Launch> kd_forward_launches(const RunCfg& rc, double2* F, int t_lo, int n_obs,
+                                               int64_t meas_stride) {
+  const dtc_problem* pr = rc.prob;
+  const int P = pr->T - 1 + pr->t_offset;
+  if (P <= 0) return {};
+  Chain fw = forward_chain(rc.pl, 1, P, dtc::kStreamForward);
+  fw.post_after_d = false;
+  tag_bond(rc, fw, 1);
+  std::vector<Launch> sched = chain_launches(rc, fw, F, n_obs, meas_stride);
+  for (Launch& l : sched) {
+    const int t = l.ps.d_index - pr->t_offset;
+    if (l.ps.diag != dtc::kDiagNone && t >= t_lo && t < pr->T) l.t_state = t;
+  }
+  return sched;
+}
+
+// The energy sweep (dtc_energy*): rows vals[T][3 L] per state -- norm, Z_i |
+// Z_i Z_i+1 | X_i -- from passes of 4 L observables (the above mid-pass + X_i
+// before the pre-kick).  Null, or the text of an internal error.
+//
+// The schedule: the forward chain one kick layer past the last period
+// (X_P, no D after it), every pass measuring in flight (meas_parts):
+//  * a pass closing period p: Z, ZZ after the diagonal and X of its sites
+//    before their post-kick X_p -> time p - t_offset;
+//  * a pass whose pre-kick is X_nd (nd diagonals applied): X of its sites
+//    before that kick -> time nd - t_offset, unless its sites' X at that
+//    time is already taken (one group: the post-kick of the previous pass).
+// Each group's X at a time is taken exactly once (checked below); the
+// reduce accumulates the X ranges into the zeroed per-time rows.
+//
+// Device-like noise: a non-unitary kick on one site changes <X> of the
+// others, so nothing is measured across a kick.  The chain starts no layer
+// in a pass that applies D (2 passes per period); after the pass closing
+// period p the state is exactly the state at p: Z, ZZ mid-pass, then X by
+// one noiseless basis-change pass per site group (E = H^L F; the engine's
+// callback at t_state).
+//
+// Bond noise (dtc_energy_bond): every pass that applies D takes the per-state
+// tables of forward layer d_index, and every kick layer after the first the
+// outgoing Pauli of the layer before it.  All of the above is measured on
+// the state before the outgoing Pauli P_t of layer t + t_offset -- mid-pass
+// after D, before the post-kick or the next pass's pre-kick that absorbs
+// P_t, and on the X-basis rotation of that same state -- so one sign pass
+// over the finished rows (launch_bond_obs_sign) applies P_t to all of them.
+inline const char* build_energy_schedule(const RunCfg& rc, double2* F, double* vals,
+                                         std::vector<Launch>& sched) {
+  const Plan& pl = rc.pl;
+  const dtc_problem* pr = rc.prob;
+  const int T = pr->T, P = T - 1 + pr->t_offset, G = (int)pl.groups.size();
+  const int n_v = 3 * pl.L, n_obs = 4 * pl.L;
+  const int64_t stride = (int64_t)T * n_v;
+  auto row = [&](int t) { return vals + (size_t)t * n_v; };
+  sched.clear();
+  if (P <= 0) return nullptr;
+  if (rc.device) {
+    sched = kd_forward_launches(rc, F, 0, n_obs, stride);
+    for (Launch& l : sched)
+      if (l.t_state >= 0) {
+        l.meas_mode = dtc::kMeasEnergy;
+        l.meas_parts = dtc::kPartZ;
+        l.energy_row = row(l.t_state);
+      }
+    return nullptr;
+  }
+  Chain fw = forward_chain(pl, 1, P + 1, dtc::kStreamForward);
+  fw.trailing_d = false;
+  fw.X[P].row = P - 1;  // never observed: any valid table row
+  tag_bond(rc, fw, 1);
+  sched = chain_launches(rc, fw, F, n_obs, stride);
+  std::vector<char> x_done((size_t)T * G, 0);
+  for (Launch& l : sched) {
+    const PassSpec& ps = l.ps;
+    const bool closes = ps.diag != dtc::kDiagNone;
+    const int g = ps.group, t = ps.d_index - pr->t_offset;
+    if (closes && t >= 0 && t < T) {
+      l.meas_parts |= dtc::kPartZ;
+      l.energy_row = row(t);
+      if (ps.post.enabled) {
+        l.meas_parts |= dtc::kPartXPost;
+        x_done[(size_t)t * G + g] = 1;
+      }
+    }
+    // (nd: the diagonals applied before this pass)
+    const int nd = ps.d_index - (closes ? 1 : 0), te = nd - pr->t_offset;
+    if (ps.pre.enabled && nd >= 1 && te >= 0 && te < T && !x_done[(size_t)te * G + g]) {
+      l.meas_parts |= dtc::kPartXPre;
+      l.energy_row_pre = row(te);
+      x_done[(size_t)te * G + g] = 1;
+    }
+    if (l.meas_parts) l.meas_mode = dtc::kMeasEnergy;
+  }
+  for (int t = 0; t < T; ++t)
+    for (int g = 0; g < G; ++g)
+      if (t + pr->t_offset >= 1 && !x_done[(size_t)t * G + g])
+        return "internal: dtc_energy left an X group unmeasured";
+  // the extra kick layer's pass only measures X: its state is never read
+  Launch& last = sched.back();
+  if (sched.size() >= 2 && pass_shape(last.ps) == dtc::kShapeK &&
+      (last.meas_parts & dtc::kPartXPre) && !(last.meas_parts & dtc::kPartZ))
+    last.no_store = 1;
+  return nullptr;
+}
+
+// The sampling sweep (dtc_sample): the K-D chain, every time t_first <= t < T
+// past the initial state sampled from the state its closing pass leaves --
+// as the energy sweep keeps it under device-like noise, here with the unitary
+// kick kinds.
+inline std::vector<Launch> build_sample_schedule(const RunCfg& rc, double2* F) {
+  return kd_forward_launches(rc, F, rc.prob->t_first, 0, 0);
+}
+
+// The forward prefix (dtc_prefix_build): periods 1 .. n_periods in place,
+// post_after_d as the autocorrelator's forward chain, so no kick is pending.
+inline std::vector<Launch> build_prefix_schedule(const RunCfg& rc, int n_periods, double2* F) {
+  Chain fw = forward_chain(rc.pl, 1, n_periods, dtc::kStreamForward);
+  fw.post_after_d = !rc.device;
+  return chain_launches(rc, fw, F, 2, 0);
+}
+
 // ---- the canonical listing of a schedule ------------------------------------
 // One line per launch with every field of Launch (tools/schedule_check.cpp,
 // and DTC_PRINT_SCHED in development builds).  A pointer prints as the role of
@@ -1323,6 +1502,10 @@ inline void dump_schedule(std::FILE* f, const std::vector<Launch>& sched,
     }
     std::fprintf(f, " parts=%d", l.meas_parts);
     dump_ptr(f, "energy_row", l.energy_row, roles);
+    // (the forward sweeps' fields, only where set: the autocorrelator's listings
+    // stay as they were recorded)
+    if (l.energy_row_pre) dump_ptr(f, "row_pre", l.energy_row_pre, roles);
+    if (l.t_state >= 0) std::fprintf(f, " t_state=%d", l.t_state);
     std::fprintf(f, "\n");
   }
 }

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import dm_oracle, energy_oracle
-from tests.helpers import harsh_device, random_disorder
+from tests.helpers import harsh_device, implied_launch_counts, random_disorder
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -182,3 +182,24 @@ def test_energy_sums_match_trajectory_rows(pkg, engine, L, T, n_inst, n_traj, ba
     e_ro = pkg.energy.get_instances_energy(spec, n_traj, seed=44, engine=engine, traj_offset=3,
                                            readout=readout)["full"]
     assert np.abs(e_ro - np.stack(per_traj)).max() < 1e-11
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_energy_launches_match_schedule_dump(pkg, tmp_path, device):
+    """The engine streams exactly the launches that the schedule header builds
+    (tools/schedule_check.cpp mode=energy, the same case on the CPU): passes by
+    kind and reduces, three trajectories in one batch.  L = 14: two site groups."""
+    rng = np.random.default_rng(61)
+    L, T = 14, 4
+    hs, phis = random_disorder(rng, L)
+    kw = {"device": harsh_device(pkg, L)} if device else {"noise_prob": 0.05}
+    spec = pkg.energy.energy_spec(L, T, hs, phis, 0.94, "vacuum", **kw)
+    want, _ = implied_launch_counts(
+        pkg, tmp_path, ["mode=energy", "L=%d" % L, "T=%d" % T,
+                        "noise=" + ("device" if device else "depol")],
+        n_groups=2, x_basis=True, measured_x=True)
+    with pkg.DtcEngine(0) as eng:
+        eng.set_profiling(True)
+        eng.energy(spec, 3, seed=21)
+        st = eng.kernel_stats()
+    assert {k: st[k]["launches"] for k in want} == want

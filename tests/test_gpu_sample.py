@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from tests import sample_model as sm
-from tests.helpers import random_disorder
+from tests.helpers import implied_launch_counts, random_disorder
 
 pytestmark = pytest.mark.gpu
 
@@ -191,6 +191,27 @@ def test_sample_profiling_books_reduce(pkg):
     assert st["launches"] == 2 * 2 * (T - 1)
     pick = n * 2 * (8.0 * 2 + 16.0 * 4096)
     assert st["bytes"] == pytest.approx(2 * (T - 1) * (16.0 * (1 << L) * n + pick))
+
+
+def test_sample_launches_match_schedule_dump(pkg, tmp_path):
+    """The engine streams exactly the launches that the schedule header builds
+    (tools/schedule_check.cpp mode=sample, the same case on the CPU): passes by
+    kind, and under the reduce kind the two sampling launches per (time, basis);
+    three trajectories in one batch, both bases, four shots.  L = 14: two site
+    groups."""
+    rng = np.random.default_rng(62)
+    L, T = 14, 3
+    hs, phis = random_disorder(rng, L)
+    spec = pkg.SweepSpec(L=L, T=T, hs=hs, phis=phis, g=0.95, noise_prob=0.05)
+    want, n_times = implied_launch_counts(pkg, tmp_path, ["mode=sample", "L=%d" % L, "T=%d" % T],
+                                          n_groups=2, x_basis=True, measured_x=False)
+    assert n_times == T - 1
+    want[pkg._capi.KERNEL_REDUCE] += 2 * 2 * n_times
+    with pkg.DtcEngine(0) as eng:
+        eng.set_profiling(True)
+        eng.sample(spec, 3, n_shots=4, seed=1)
+        st = eng.kernel_stats()
+    assert {k: st[k]["launches"] for k in want} == want
 
 
 def test_sample_cli(pkg, tmp_path):

@@ -1,10 +1,11 @@
-"""The autocorrelator's batch schedules (csrc/dtc_schedule.h) on the CPU:
+"""The batch schedules (csrc/dtc_schedule.h) on the CPU:
 tools/schedule_check.cpp builds the schedule of a case exactly as the engine's
-autocorr_impl does and dumps every field of every launch.  Each case of
-tests/golden/schedules.json -- the headline line, each scheduling option off,
-the wavefront threshold, device-like and bond noise, the energy echo, per-site
-Z, a prefix, every plan shape -- must give the recorded tally and dump hash, and
-every dump must have the structure the engine relies on.  A change that alters
+autocorr_impl, energy_impl or dtc_sample does and dumps every field of every
+launch.  Each case of tests/golden/schedules.json -- the headline line, each
+scheduling option off, the wavefront threshold, device-like and bond noise, the
+energy echo, per-site Z, a prefix, every plan shape; the energy and sampling
+sweeps (mode=energy, mode=sample) -- must give the recorded tally and dump hash,
+and every dump must have the structure the engine relies on.  A change that alters
 a schedule shows up here first (tools/schedule_golden.py refreshes the file for
 one that is meant to).  Built plain and with the host sanitizers; a stand-alone
 binary either way."""
@@ -24,9 +25,19 @@ PKG = "noise-resilience-in-discrete-time-crystal-realizations-on-quantum-compute
 WARN = ["-Wall", "-Wextra", "-Werror", "-Wno-missing-field-initializers", "-Wno-unknown-pragmas"]
 SANITIZE = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 K_SHAPE, KD_SHAPE, KDK_SHAPE, WF_SHAPE = 0, 1, 3, -2
+PART_Z, PART_XPOST, PART_XPRE = 1, 2, 4
 
 with open(os.path.join(ROOT, "tests", "golden", "schedules.json")) as _f:
     CASES = json.load(_f)["cases"]
+
+
+def mode_of(c):
+    return dict(tok.split("=", 1) for tok in c["args"]).get("mode", "autocorr")
+
+
+AUTOCORR_CASES = [c for c in CASES if mode_of(c) == "autocorr"]
+ENERGY_CASES = [c for c in CASES if mode_of(c) == "energy"]
+SAMPLE_CASES = [c for c in CASES if mode_of(c) == "sample"]
 
 
 def build(out_dir, flags):
@@ -103,7 +114,7 @@ def test_schedule_matches_golden(dumps, case):
     assert hashlib.sha256(dump.encode()).hexdigest() == case["sha256"]
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+@pytest.mark.parametrize("case", AUTOCORR_CASES, ids=[c["name"] for c in AUTOCORR_CASES])
 def test_schedule_structure(dumps, case):
     a = case_args(case)
     L, T, t_off, t_first = (int(a[k]) for k in ("L", "T", "t_offset", "t_first"))
@@ -146,6 +157,75 @@ def test_schedule_structure(dumps, case):
         assert all(l["meas"][0] == 1 and l["parts"] == 0 for l in ends)
         echo_rows = [offset(l["meas_out"], "vals_e") // 2 for l in ends]
     assert echo_rows == (times if a["want_echo"] == "1" or energy else [])
+
+
+def site_groups(L):
+    """How many site groups make_plan gives L sites: 12 in the low group, then
+    up to 9 per further group."""
+    return 1 if L <= 12 else 1 + (L - 12 + 8) // 9
+
+
+@pytest.mark.parametrize("case", ENERGY_CASES, ids=[c["name"] for c in ENERGY_CASES])
+def test_energy_schedule_structure(dumps, case):
+    """The rules of the energy sweep (the comment of build_energy_schedule), not
+    its builder: which launch measures what into which time row."""
+    a = case_args(case)
+    L, T, t_off = (int(a[k]) for k in ("L", "T", "t_offset"))
+    G = site_groups(L)
+    sched = parse(dumps[case["name"]])
+    times = [t for t in range(T) if t + t_off >= 1]
+    assert bool(sched) == (T - 1 + t_off > 0)
+    for l in sched:
+        assert l["src"] == l["dst"] == "F+0" and l["dst2"] == "-" and l["basis"] == "-", l
+        assert l["meas"] == [3 if l["parts"] else 0, 0, 4 * L], l
+        assert l["meas_out"] == "-" and int(l["meas_stride"]) == T * 3 * L, l
+        assert (l["energy_row"] != "-") == bool(l["parts"] & PART_Z), l
+        assert ("row_pre" in l) == bool(l["parts"] & PART_XPRE), l
+    z_rows = [offset(l["energy_row"], "vals") for l in sched if l["parts"] & PART_Z]
+    assert z_rows == [t * 3 * L for t in times]
+    has_d = [l for l in sched if l["ps"]["diag"] != "0"]
+    bond = a["noise"] in ("bond", "device_bond")
+    for l in sched:
+        want = "1,0,%s,0" % l["ps"]["d"] if bond and l in has_d else "0,0,0,0"
+        assert l["bond"] == want, l
+    if a["noise"] in ("device", "device_bond"):
+        # nothing measured across a kick: K-D passes, the closing pass of each
+        # measured time takes Z and leaves that time's state
+        assert all(l["ps"]["post"] == "-" for l in has_d)
+        assert all(("t_state" in l) == bool(l["parts"] & PART_Z) for l in sched)
+        assert all(l["parts"] in (0, PART_Z) and not l["no_store"] for l in sched)
+        assert [int(l["t_state"]) for l in sched if "t_state" in l] == times
+        return
+    assert all("t_state" not in l for l in sched)
+    # each (time, group) X exactly once: before the post-kick of the pass that
+    # closes the time, or at the entry of a later pass on the group
+    taken = []
+    for l in sched:
+        assert not l["parts"] & PART_XPOST or l["parts"] & PART_Z, l
+        if l["parts"] & PART_XPOST:
+            taken.append((offset(l["energy_row"], "vals") // (3 * L), int(l["ps"]["g"])))
+        if l["parts"] & PART_XPRE:
+            taken.append((offset(l["row_pre"], "vals") // (3 * L), int(l["ps"]["g"])))
+    assert sorted(taken) == [(t, g) for t in times for g in range(G)]
+    for i, l in enumerate(sched):
+        if l["no_store"]:
+            assert i == len(sched) - 1 and l["shape"] == K_SHAPE, l
+            assert l["parts"] & PART_XPRE and not l["parts"] & PART_Z, l
+
+
+@pytest.mark.parametrize("case", SAMPLE_CASES, ids=[c["name"] for c in SAMPLE_CASES])
+def test_sample_schedule_structure(dumps, case):
+    a = case_args(case)
+    T, t_off, t_first = (int(a[k]) for k in ("T", "t_offset", "t_first"))
+    sched = parse(dumps[case["name"]])
+    assert sched
+    for l in sched:
+        assert l["src"] == l["dst"] == "F+0" and l["dst2"] == "-" and not l["no_store"], l
+        assert l["meas"][0] == 0 and l["parts"] == 0 and l["bond"] == "0,0,0,0", l
+        assert "t_state" not in l or l["ps"]["diag"] != "0", l
+    assert all(l["ps"]["post"] == "-" for l in sched if l["ps"]["diag"] != "0")
+    assert ([int(l["t_state"]) for l in sched if "t_state" in l]
+            == list(range(max(t_first, 1 - t_off), T)))
 
 
 def test_headline_counts_are_exact(dumps):

@@ -1,5 +1,6 @@
-// Stand-alone dump of the autocorrelator's batch schedule (csrc/dtc_schedule.h),
-// host only, no GPU:
+// Stand-alone dump of a batch schedule (csrc/dtc_schedule.h) -- the
+// autocorrelator's, the energy sweep's or the sampling sweep's -- host only, no
+// GPU:
 //
 //   g++ -std=c++17 -O1 -D__HIP_PLATFORM_AMD__ -I <rocm>/include -I <pkg>/csrc
 //       tools/schedule_check.cpp -o schedule_check
@@ -15,6 +16,10 @@
 //   kick=x|y|xy_cycle|gen     noise=none|depol|device|bond|device_bond
 //   zsite energy want_fwd want_echo                   0 / 1
 //   lightcone lc_wide lc_wide3 dual runahead wavefront split13   0 / 1;  wf_cap
+//   mode=autocorr|energy|sample   energy: build_energy_schedule as energy_impl
+//     calls it, sample: build_sample_schedule as dtc_sample does (noise none or
+//     depol); the buffers are F, E and vals, and the tally adds the launches
+//     that leave a time's state (t_state) and the Z, XPost and XPre parts
 // tests/test_schedule_cpu.py compares the dumps with tests/golden/schedules.json
 // (it may also be built with -fsanitize=address,undefined and run as it is).
 #include <cmath>
@@ -68,7 +73,7 @@ int main(int argc, char** argv) {
       {"zsite", "0"},     {"energy", "0"},   {"want_fwd", "1"}, {"want_echo", "1"},
       {"n_pre", "0"},     {"octet", "6"},    {"lightcone", "1"}, {"lc_wide", "1"},
       {"lc_wide3", "1"},  {"dual", "1"},     {"runahead", "1"}, {"wavefront", "1"},
-      {"wf_cap", "4"},    {"split13", "0"}};
+      {"wf_cap", "4"},    {"split13", "0"},  {"mode", "autocorr"}};
   for (int i = 1; i < argc; ++i) {
     const char* eq = std::strchr(argv[i], '=');
     const std::string key(argv[i], eq ? (size_t)(eq - argv[i]) : 0);
@@ -81,6 +86,9 @@ int main(int argc, char** argv) {
   if (noise != "none" && noise != "depol" && noise != "device" && noise != "bond" &&
       noise != "device_bond")
     return usage("bad noise");
+  const std::string mode = a["mode"];
+  if (mode != "autocorr" && mode != "energy" && mode != "sample") return usage("bad mode");
+  const bool autocorr = mode == "autocorr";
   const bool device = noise == "device" || noise == "device_bond";
   const bool bond = noise == "bond" || noise == "device_bond";
   const bool zsite = num("zsite") != 0, energy = num("energy") != 0;
@@ -102,6 +110,8 @@ int main(int argc, char** argv) {
     return usage("problem out of range");
   if (bond && pr.t_offset != 0) return usage("bond noise needs t_offset = 0");
   if (energy && (device || bond || zsite || n_pre)) return usage("the energy echo runs alone");
+  if (!autocorr && (energy || zsite || n_pre)) return usage("a forward sweep takes no autocorr key");
+  if (mode == "sample" && (device || bond)) return usage("sampling runs depolarizing or noiseless");
   if (bond && n_pre) return usage("bond noise runs without a prefix");
   const int P = pr.T - 1 + pr.t_offset;
   if (n_pre < 0 || (n_pre && (zsite || pr.t_first + pr.t_offset <= n_pre || P <= n_pre)))
@@ -133,7 +143,8 @@ int main(int argc, char** argv) {
   rc.n_traj = 1;
   rc.noisy = noise != "none";
   rc.row_kind = classify_rows(&pr);
-  rc.pl = autocorr_plan(pr.L, rc.row_kind, so, !device && !zsite && !n_pre && !bond && !energy);
+  rc.pl = autocorr_plan(pr.L, rc.row_kind, so,
+                        autocorr && !device && !zsite && !n_pre && !bond && !energy);
   rc.device = device;
   rc.bond = bond;
   rc.octet_bits = num("octet");
@@ -158,6 +169,31 @@ int main(int argc, char** argv) {
   WfTables wt;
   std::vector<Launch> sched;
   SchedInfo info;
+  if (!autocorr) {
+    // the forward sweeps: F, E and the rows (fake addresses as above)
+    const char* err = nullptr;
+    if (mode == "energy") err = build_energy_schedule(rc, bufs.F, bufs.vals_f, sched);
+    else sched = build_sample_schedule(rc, bufs.F);
+    if (err) {
+      std::printf("error %s\n", err);
+      return 1;
+    }
+    dump_schedule(stdout, sched, {{"F", bufs.F, span, 16}, {"E", bufs.E, span, 16},
+                                  {"vals", bufs.vals_f, span, 8}});
+    int shape[6] = {}, t_states = 0, z = 0, xpost = 0, xpre = 0;
+    for (const Launch& l : sched) {
+      const int s = pass_shape(l.ps);
+      if (s >= 0 && s < 6) ++shape[s];
+      t_states += l.t_state >= 0;
+      z += (l.meas_parts & dtc::kPartZ) != 0;
+      xpost += (l.meas_parts & dtc::kPartXPost) != 0;
+      xpre += (l.meas_parts & dtc::kPartXPre) != 0;
+    }
+    std::printf("tally launches=%zu K=%d KD=%d DK=%d KDK=%d D=%d t_state=%d Z=%d XPost=%d XPre=%d\n",
+                sched.size(), shape[dtc::kShapeK], shape[dtc::kShapeKD], shape[dtc::kShapeDK],
+                shape[dtc::kShapeKDK], shape[dtc::kShapeD], t_states, z, xpost, xpre);
+    return 0;
+  }
   if (const char* err = build_autocorr_schedule(rc, so, rq, bufs, wt, sched, info)) {
     std::printf("error %s\n", err);
     return 1;

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Refresh tests/golden/schedules.json from tools/schedule_check.cpp.
+"""Complete tests/golden/schedules.json from tools/schedule_check.cpp.
 
-Every case of the file keeps its name and arguments; its tally and the SHA-256
-of its dump are replaced by what the driver prints now, and the three cases
-with the fewest launches keep their full dump.  Run it only for a change that
-is meant to alter a schedule, and read the diff of the dumps it keeps.
+A new case is an entry with its name and arguments only: it gets the tally and
+the SHA-256 of the dump the driver prints now.  The recorded cases stay as they
+are.  With --refresh every case is recorded anew, and the three autocorrelator
+cases with the fewest launches keep their full dump: only for a change that is
+meant to alter a schedule, and read the diff of the dumps it keeps.  --check
+writes nothing and tells whether every case still gives what is recorded.
 
-    python tools/schedule_golden.py [--check]
+    python tools/schedule_golden.py [--check | --refresh]
 """
 import hashlib
 import json
@@ -55,12 +57,19 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         exe = build(tmp)
         dumps = {c["name"]: run(exe, c["args"]) for c in golden["cases"]}
+    refresh = "--refresh" in sys.argv
     fresh = []
     for c in golden["cases"]:
+        if "sha256" in c and not (refresh or "--check" in sys.argv):
+            fresh.append(c)
+            continue
         tally, sha = digest(dumps[c["name"]])
         fresh.append({"name": c["name"], "args": c["args"], "tally": tally, "sha256": sha})
+        if "dump" in c and not refresh:
+            fresh[-1]["dump"] = dumps[c["name"]].splitlines()
     n_launches = {n: sum(ln.startswith("sched ") for ln in d.splitlines()) for n, d in dumps.items()}
-    for c in sorted(fresh, key=lambda c: (n_launches[c["name"]], c["name"]))[:3]:
+    autocorr = [c for c in fresh if not any(a.startswith("mode=") for a in c["args"])]
+    for c in sorted(autocorr, key=lambda c: (n_launches[c["name"]], c["name"]))[:3 if refresh else 0]:
         c["dump"] = dumps[c["name"]].splitlines()
     if "--check" in sys.argv:
         same = golden["cases"] == fresh
