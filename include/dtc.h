@@ -297,6 +297,54 @@ int dtc_shard_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* prob, const d
 int dtc_shard_exchange_slice(dtc_ctx* ctx, const dtc_shard* shard, int32_t slice_bits,
                              int32_t slice, double* state);
 
+/* ---- The echo on a sharded state (fast.py:140-143 on the layout above).
+ * Chain t (p = t + prob->t_offset periods forward, F_p the state after them):
+ *   E_t = K'_p ... D* K'_2 D* K'_1 D* F_p,  echo[t] ~ <Z_j>(E_t),
+ * draw for draw dtc_autocorr's echo chain of that trajectory.  Layer k of
+ * chain t, L_k:
+ *   k = 0       the exact undo of the forward layer K_{p+1} (kick row p, forward
+ *               stream 0, counter p + 1): the forward's fused step runs K_{p+1}
+ *               ahead on its post_mask, and a chain forked there undoes it first
+ *   1 <= k <= p K'_k, the inverse kick layer of period p - k + 1 (kick row
+ *               p - k, sub-gates reversed and daggered, draws of RNG stream
+ *               1 + t, counter k)
+ * and D* is the conjugated RZZ+RZ layer (no communication, like D).  The four
+ * calls below are their forward twins with (t, k) in place of `period`: the
+ * same arguments otherwise, the same checks, plus 0 <= t < T, 0 <= k <= p and
+ * every row used inside the kick table.
+ *
+ * dtc_shard_echo_step:  dst = L_{k+1}[post_mask] . (D*)^diag . L_k[pre_mask] . src
+ * (post_mask must be 0 when k = p; src != dst forks a chain off the forward
+ * buffer without a copy).  dst == NULL is a chain's end: with diag = 0,
+ * post_mask = 0, a non-empty pre_mask inside one site group and obs given, one
+ * kick-only pass measures obs at its end and stores nothing (16 B per
+ * amplitude, DTC_KERNEL_FINAL_PASS); any other call with dst == NULL is
+ * DTC_EINVAL.  An inverse period has the forward's shape mirrored: the fused
+ * step after an exchange (pre = K'_k on the bits that just became local, D*,
+ * post = K'_{k+1} on the top group), K'_{k+1} on the other local bits slice by
+ * slice, the exchange (sharded.py: sharded_autocorr_pipelined). */
+int dtc_shard_echo_step(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                        const dtc_shard* shard, uint64_t seed, int64_t traj, int32_t inst,
+                        int32_t t, int32_t k, uint64_t pre_mask, int32_t diag,
+                        uint64_t post_mask, const double* src, double* dst, double* obs);
+int dtc_shard_echo_step_async(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                              const dtc_shard* shard, uint64_t seed, int64_t traj, int32_t inst,
+                              int32_t t, int32_t k, uint64_t pre_mask, int32_t diag,
+                              uint64_t post_mask, const double* src, double* dst,
+                              double* obs_dev);
+/* L_k of chain t on the local bits pre_mask of one slice (dtc_shard_kick_slice),
+ * and the same fused with the slice's in-place exchange
+ * (dtc_shard_kick_exchange_slice: unitary kick kinds, else the two calls). */
+int dtc_shard_echo_kick_slice(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                              const dtc_shard* shard, uint64_t seed, int64_t traj, int32_t t,
+                              int32_t k, uint64_t pre_mask, int32_t chunk_bits,
+                              int32_t slice_bits, int32_t slice, double* state);
+int dtc_shard_echo_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* prob,
+                                       const dtc_noise* noise, const dtc_shard* shard,
+                                       uint64_t seed, int64_t traj, int32_t t, int32_t k,
+                                       uint64_t pre_mask, int32_t slice_bits, int32_t slice,
+                                       double* state);
+
 /* The ctx's HIP stream (hipStream_t), for ordering host-side collectives
  * against the asynchronous entry points; and a wait for everything on it. */
 int dtc_get_stream(dtc_ctx* ctx, void** stream);
@@ -477,7 +525,7 @@ int dtc_sample_state(const double* state, int32_t L, int32_t basis, const double
 #define DTC_KERNEL_REDUCE 2    /* per-state observable reduction; bond-noise sign pass;
                                   measurement sampling (weights, picks) */
 #define DTC_KERNEL_INIT 3      /* preparation: bond-noise diagonal table builder */
-#define DTC_KERNEL_FINAL_PASS 4 /* last pass of an echo chain: measure, no store */
+#define DTC_KERNEL_FINAL_PASS 4 /* last pass of an echo chain (sharded ones too): measure, no store */
 #define DTC_KERNEL_EXCHANGE 5  /* virtual ranks' in-place slice exchange        */
 #define DTC_KERNEL_KINDS 6
 /* total_bytes = algorithmic HBM bytes of the launches: 32 B per amplitude for a

@@ -60,6 +60,10 @@ EXPORTED_SYMBOLS = (
     "dtc_sample",
     "dtc_sample_draws",
     "dtc_sample_state",
+    "dtc_shard_echo_step",
+    "dtc_shard_echo_step_async",
+    "dtc_shard_echo_kick_slice",
+    "dtc_shard_echo_kick_exchange_slice",
 )
 
 KERNEL_LO_PASS = 0
@@ -75,7 +79,8 @@ KERNEL_NAMES = {
                    "sample_weights_kernel / sample_pick_kernel (measurement sampling)",
     KERNEL_INIT: "bond_diag_kernel (bond-noise diagonal tables per state, dtc_autocorr_bond)",
     KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split / the last dtc_xend_pass of an energy "
-                       "echo chain (measure only, no store)",
+                       "echo chain / dtc_kick_sites_final, the end of a sharded echo chain "
+                       "(measure only, no store)",
     KERNEL_EXCHANGE: "exchange_swap_kernel (virtual ranks' in-place slice exchange)",
 }
 
@@ -239,6 +244,27 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
             ctypes.c_void_p, P(DtcProblem), P(DtcNoise), P(DtcShard), ctypes.c_uint64,
             ctypes.c_int64, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
             ctypes.c_void_p,
+        ]
+        # the echo twins: (t, k) in place of `period`
+        lib.dtc_shard_echo_step.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), P(DtcShard), ctypes.c_uint64,
+            ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+            ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, _dp,
+        ]
+        lib.dtc_shard_echo_step_async.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), P(DtcShard), ctypes.c_uint64,
+            ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+            ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ]
+        lib.dtc_shard_echo_kick_slice.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), P(DtcShard), ctypes.c_uint64,
+            ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+            ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+        ]
+        lib.dtc_shard_echo_kick_exchange_slice.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), P(DtcShard), ctypes.c_uint64,
+            ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+            ctypes.c_int32, ctypes.c_void_p,
         ]
         lib.dtc_get_stream.argtypes = [ctypes.c_void_p, P(ctypes.c_void_p)]
         lib.dtc_synchronize.argtypes = [ctypes.c_void_p]

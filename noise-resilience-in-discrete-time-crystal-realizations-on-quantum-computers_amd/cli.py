@@ -10,7 +10,10 @@ options.  Output: the same folder and ``autocorr_data_*.csv`` as fast.py:56-59,
 reference's draw-*.py scripts read it unchanged.  ``--device_name`` and
 ``--randomphi/--phi_delta/--phi_amplitude`` only enter file names, as in the
 reference.  Under torchrun the trajectories are sharded over ranks (one GPU
-per rank) and gathered on rank 0.
+per rank) and gathered on rank 0.  ``--state_shards K`` instead splits every
+state over 2^K shards (L = 33, 34: sharded.sharded_autocorr_pipelined), as
+virtual ranks of one process or one shard per rank of a 2^K-rank torchrun job;
+same CSV, both columns.
 """
 from __future__ import annotations
 
@@ -76,6 +79,10 @@ def build_parser():
                    help="1 = every t from its own trajectories (uncorrelated across t, as the "
                         "reference's circuit per t, fast.py:219-221; O(T^2) periods); 0 = the "
                         "echo branches off one forward trajectory (correlated across t)")
+    p.add_argument("--state_shards", type=int, default=0,
+                   help="K > 0: every state split over 2^K shards (sharded.py; L = 33, 34) -- "
+                        "virtual ranks in one process, or one shard per rank under torchrun "
+                        "with 2^K ranks; depolarizing or noiseless kicks only")
     return p
 
 
@@ -123,8 +130,32 @@ def main(argv=None):
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    if args.state_shards < 0:
+        raise SystemExit("--state_shards must be >= 0")
+    if args.state_shards:
+        # refused before any engine is opened
+        try:
+            sw.refuse_state_shards(spec, bool(args.independent_t))
+        except ValueError as e:
+            raise SystemExit(f"--state_shards: {e}")
+        if world not in (1, 1 << args.state_shards):
+            raise SystemExit("--state_shards K runs in one process or under torchrun with 2^K "
+                             "ranks")
     t0 = time.time()
-    if world > 1:
+    if args.state_shards:
+        group = None
+        if world > 1:
+            import torch
+            import torch.distributed as dist
+
+            torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+            if not dist.is_initialized():
+                dist.init_process_group("nccl")
+        res = sw.run_sharded_state_sweep(spec, args.state_shards, n_traj, shots=shots,
+                                         seed=args.seed, rank=rank, world=world, group=group)
+        if rank != 0:
+            return 0
+    elif world > 1:
         from .distributed import sharded_sweep
 
         res = sharded_sweep(spec, n_traj, shots=shots, seed=args.seed, batch=args.batch,

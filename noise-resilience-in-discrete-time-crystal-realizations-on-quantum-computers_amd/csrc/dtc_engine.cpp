@@ -2334,38 +2334,85 @@ RunCfg shard_runcfg(const dtc_problem* pr, const dtc_noise* nz, const dtc_shard*
   return rc;
 }
 
-// dtc_shard_step / dtc_shard_step_async: obs is a host array (copied, then
-// the stream is synchronised) or, when obs_on_device, a device array the
-// reduction writes directly (nothing waits).
+// A kick layer of a sharded step: kick-table row, KickMode, RNG stream and
+// counter (the mask a call gives says which bits take it).
+struct ShardLayer {
+  int row, mode;
+  uint32_t stream, counter;
+};
+// The layers a step addresses: dst = post . D^diag . pre . src, D in diag_mode.
+struct ShardLayers {
+  ShardLayer pre, post;
+  int diag_mode;
+};
+
+// forward: K_period, then D, then K_{period+1} (stream 0, counter = period)
+ShardLayer shard_forward_layer(int period) {
+  return ShardLayer{period - 1, dtc::kKickForward, dtc::kStreamForward, (uint32_t)period};
+}
+ShardLayers shard_forward_layers(int period) {
+  return ShardLayers{shard_forward_layer(period), shard_forward_layer(period + 1), dtc::kDiagFwd};
+}
+// echo chain t, layer k (p = t + t_offset; echo_chain's layers in dtc_schedule.h):
+// k = 0 the exact undo of the forward layer K_{p+1} that ran ahead, 1 <= k <= p
+// the inverse kick K'_k of period p - k + 1 (stream 1 + t, counter k)
+ShardLayer shard_echo_layer(int t, int p, int k) {
+  if (k == 0) return ShardLayer{p, dtc::kKickUndo, dtc::kStreamForward, (uint32_t)(p + 1)};
+  return ShardLayer{p - k, dtc::kKickInverse, (uint32_t)(1 + t), (uint32_t)k};
+}
+int shard_echo_check(const dtc_problem* pr, int32_t t, int32_t k) {
+  if (!pr) return fail(DTC_EINVAL, "null problem");
+  if (t < 0 || t >= pr->T) return fail(DTC_EINVAL, "t outside [0, T)");
+  if (k < 0 || k > t + pr->t_offset) return fail(DTC_EINVAL, "k outside [0, t + t_offset]");
+  return DTC_OK;
+}
+
+dtc::KickDesc shard_kick_desc(const ShardLayer& ly, const Group& g, uint64_t mask) {
+  return dtc::KickDesc{1, ly.row, ly.mode, ly.stream, ly.counter, skip_bits(g, mask)};
+}
+
+// dtc_shard_step / dtc_shard_step_async and their echo twins: obs is a host
+// array (copied, then the stream is synchronised) or, when obs_on_device, a
+// device array the reduction writes directly (nothing waits).  no_dst_ok (the
+// echo twins): dst == NULL runs the chain's end, one kick-only pass that
+// measures and stores nothing.
 int shard_step_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                     const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t inst,
-                    int32_t period, uint64_t pre_mask, int32_t diag, uint64_t post_mask,
-                    const double* src, double* dst, double* obs, bool obs_on_device) {
-  if (!src || !dst) return fail(DTC_EINVAL, "null src/dst");
+                    const ShardLayers& ly, uint64_t pre_mask, int32_t diag, uint64_t post_mask,
+                    const double* src, double* dst, double* obs, bool obs_on_device,
+                    bool no_dst_ok = false) {
+  if (!src || (!dst && !no_dst_ok)) return fail(DTC_EINVAL, "null src/dst");
   DTC_TRY(shard_check_common(ctx, pr, nz, sh, traj, inst));
   const int nl = sh->n_local;
   const uint64_t all = nl >= 64 ? ~0ull : (1ull << nl) - 1;
   if ((pre_mask | post_mask) & ~all) return fail(DTC_EINVAL, "kick mask has non-local bits");
   if (post_mask && !diag) return fail(DTC_EINVAL, "post_mask needs diag");
   const int n_rows = std::max(1, pr->T - 1 + pr->t_offset);
-  if (pre_mask && (period < 1 || period > n_rows))
+  if (pre_mask && (ly.pre.row < 0 || ly.pre.row >= n_rows))
     return fail(DTC_EINVAL, "period outside kick table");
-  if (post_mask && period + 1 > n_rows) return fail(DTC_EINVAL, "period + 1 outside kick table");
+  if (post_mask && (ly.post.row < 0 || ly.post.row >= n_rows))
+    return fail(DTC_EINVAL, "period + 1 outside kick table");
+  if (!dst && (diag || post_mask || !pre_mask || !obs))
+    return fail(DTC_EINVAL, "dst == NULL is the measured kick-only end of a chain");
   DTC_HIP(hipSetDevice(ctx->device));
 
   RunCfg rc = shard_runcfg(pr, nz, sh, seed, traj);
   const Plan& pl = rc.pl;
   const int B = sh->n_shards;
+  if (!dst) {
+    int holding = 0;
+    for (const Group& g : pl.groups)
+      if (pre_mask & group_bits(g)) ++holding;
+    if (holding != 1) return fail(DTC_EINVAL, "dst == NULL needs the kicked bits in one site group");
+  }
   DTC_TRY(shard_tables(ctx, pr, sh, inst, pl, rc));
   const int n_obs = 1 + nl;
   DTC_TRY(ensure(ctx->partial, (size_t)B * pl.n_tiles * n_obs * sizeof(double)));
   DTC_TRY(ensure(ctx->vals_f, (size_t)B * n_obs * sizeof(double)));
   double* meas_out = obs_on_device ? obs : (double*)ctx->vals_f.p;
 
-  auto layer = [&](int p, uint64_t mask, const Group& g) {
-    dtc::KickDesc k{1, p - 1, dtc::kKickForward, dtc::kStreamForward, (uint32_t)p,
-                    skip_bits(g, mask)};
-    return k;
+  auto layer = [&](const ShardLayer& l, uint64_t mask, const Group& g) {
+    return shard_kick_desc(l, g, mask);
   };
   // main group: holds the highest kicked bit (the bits an exchange just made local)
   const uint64_t any = pre_mask | post_mask;
@@ -2379,27 +2426,33 @@ int shard_step_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   for (size_t g = 0; g < pl.groups.size(); ++g) {
     const uint64_t gb = group_bits(pl.groups[g]);
     if ((int)g != main_g && (pre_mask & gb))
-      passes.push_back(PassSpec{(int)g, layer(period, pre_mask, pl.groups[g]), no_kick(),
+      passes.push_back(PassSpec{(int)g, layer(ly.pre, pre_mask, pl.groups[g]), no_kick(),
                                 dtc::kDiagNone, 0});
   }
   const Group& mg = pl.groups[main_g];
   const uint64_t mb = group_bits(mg);
-  PassSpec mp{main_g, no_kick(), no_kick(), diag ? dtc::kDiagFwd : dtc::kDiagNone, 1};
-  if (pre_mask & mb) mp.pre = layer(period, pre_mask, mg);
-  if (post_mask & mb) mp.post = layer(period + 1, post_mask, mg);
+  PassSpec mp{main_g, no_kick(), no_kick(), diag ? ly.diag_mode : dtc::kDiagNone, 1};
+  if (pre_mask & mb) mp.pre = layer(ly.pre, pre_mask, mg);
+  if (post_mask & mb) mp.post = layer(ly.post, post_mask, mg);
   const int main_idx = (int)passes.size();
   if (mp.pre.enabled || mp.post.enabled || diag) passes.push_back(mp);
   const int meas_idx = diag ? main_idx : (int)passes.size() - 1;
   for (size_t g = 0; g < pl.groups.size(); ++g) {
     const uint64_t gb = group_bits(pl.groups[g]);
     if ((int)g != main_g && (post_mask & gb))
-      passes.push_back(PassSpec{(int)g, layer(period + 1, post_mask, pl.groups[g]), no_kick(),
+      passes.push_back(PassSpec{(int)g, layer(ly.post, post_mask, pl.groups[g]), no_kick(),
                                 dtc::kDiagNone, 0});
   }
   const double2* s2 = (const double2*)src;
   double2* d2 = (double2*)dst;
   const size_t len = (size_t)1 << nl;
-  if (passes.empty()) {
+  if (!dst) {
+    // the chain's end: its one kick-only pass measures at its end, no store
+    if (passes.size() != 1) return fail(DTC_EINVAL, "internal: measure-only end is one pass");
+    DTC_TRY(launch_pass_spec(ctx, rc, 0, B, passes[0], s2, nullptr, dtc::kMeasSites, 1, n_obs,
+                             meas_out, n_obs, nullptr, 0, 1));
+    passes.clear();
+  } else if (passes.empty()) {
     if (src != dst)
       DTC_HIP(hipMemcpyAsync(d2, s2, len * 16 * B, hipMemcpyDeviceToDevice, ctx->stream));
   }
@@ -2409,9 +2462,9 @@ int shard_step_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                              meas ? dtc::kMeasSites : dtc::kMeasNone, diag ? 0 : 1, n_obs,
                              meas ? meas_out : nullptr, n_obs));
   }
-  if (obs && passes.empty()) {
+  if (dst && obs && passes.empty()) {
     // no pass ran: measure with an identity-only kick pass over group 0
-    PassSpec ps{0, layer(1, 0, pl.groups[0]), no_kick(), dtc::kDiagNone, 0};
+    PassSpec ps{0, layer(shard_forward_layer(1), 0, pl.groups[0]), no_kick(), dtc::kDiagNone, 0};
     ps.pre.row = 0;
     DTC_TRY(launch_pass_spec(ctx, rc, 0, B, ps, d2, d2, dtc::kMeasSites, 1, n_obs, meas_out,
                              n_obs));
@@ -2425,30 +2478,25 @@ int shard_step_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
   return DTC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dtc_shard_step(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
-                   const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t inst,
-                   int32_t period, uint64_t pre_mask, int32_t diag, uint64_t post_mask,
-                   const double* src, double* dst, double* obs) {
-  return shard_step_impl(ctx, pr, nz, sh, seed, traj, inst, period, pre_mask, diag, post_mask,
-                         src, dst, obs, false);
-}
-
-int dtc_shard_step_async(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+// the echo twins' step: layers k and k + 1 of chain t around D*
+int shard_echo_step_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
                          const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t inst,
-                         int32_t period, uint64_t pre_mask, int32_t diag, uint64_t post_mask,
-                         const double* src, double* dst, double* obs_dev) {
-  return shard_step_impl(ctx, pr, nz, sh, seed, traj, inst, period, pre_mask, diag, post_mask,
-                         src, dst, obs_dev, true);
+                         int32_t t, int32_t k, uint64_t pre_mask, int32_t diag,
+                         uint64_t post_mask, const double* src, double* dst, double* obs,
+                         bool obs_on_device) {
+  if (!ctx) return fail(DTC_EINVAL, "null ctx");
+  DTC_TRY(shard_echo_check(pr, t, k));
+  const int p = t + pr->t_offset;
+  if (post_mask && k == p) return fail(DTC_EINVAL, "post_mask must be 0 at the chain's last layer");
+  const ShardLayers ly{shard_echo_layer(t, p, k), shard_echo_layer(t, p, k + 1), dtc::kDiagConj};
+  return shard_step_impl(ctx, pr, nz, sh, seed, traj, inst, ly, pre_mask, diag, post_mask, src,
+                         dst, obs, obs_on_device, true);
 }
 
-int dtc_shard_kick_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
-                         const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t period,
-                         uint64_t pre_mask, int32_t chunk_bits, int32_t slice_bits, int32_t slice,
-                         double* state) {
+int shard_kick_slice_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                          const dtc_shard* sh, uint64_t seed, int64_t traj, const ShardLayer& ly,
+                          uint64_t pre_mask, int32_t chunk_bits, int32_t slice_bits,
+                          int32_t slice, double* state) {
   if (!state) return fail(DTC_EINVAL, "null state");
   DTC_TRY(shard_check_common(ctx, pr, nz, sh, traj, 0));
   const int nl = sh->n_local;
@@ -2461,7 +2509,7 @@ int dtc_shard_kick_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* n
   if (pre_mask & ~low) return fail(DTC_EINVAL, "slice kick mask reaches the chunk/slice bits");
   const int n_rows = std::max(1, pr->T - 1 + pr->t_offset);
   if (!pre_mask) return DTC_OK;
-  if (period < 1 || period > n_rows) return fail(DTC_EINVAL, "period outside kick table");
+  if (ly.row < 0 || ly.row >= n_rows) return fail(DTC_EINVAL, "period outside kick table");
   const int64_t n_pieces = (int64_t)sh->n_shards << chunk_bits;
   if (n_pieces > 65535) return fail(DTC_EINVAL, "too many chunks x shards for one launch");
   DTC_HIP(hipSetDevice(ctx->device));
@@ -2480,18 +2528,17 @@ int dtc_shard_kick_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* n
     if (!(pre_mask & gb)) continue;
     if (gb & ~low) return fail(DTC_EINVAL, "a site group of the kick mask reaches the slice bits");
     PassSpec ps{(int)g, no_kick(), no_kick(), dtc::kDiagNone, 0};
-    ps.pre = dtc::KickDesc{1, period - 1, dtc::kKickForward, dtc::kStreamForward,
-                           (uint32_t)period, skip_bits(G, pre_mask)};
+    ps.pre = shard_kick_desc(ly, G, pre_mask);
     DTC_TRY(launch_pass_spec(ctx, rc, 0, (int)n_pieces, ps, base, base, dtc::kMeasNone, 1, 2,
                              nullptr, 0));
   }
   return DTC_OK;
 }
 
-int dtc_shard_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
-                                  const dtc_shard* sh, uint64_t seed, int64_t traj,
-                                  int32_t period, uint64_t pre_mask, int32_t slice_bits,
-                                  int32_t slice, double* state) {
+int shard_kick_exchange_slice_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                                   const dtc_shard* sh, uint64_t seed, int64_t traj,
+                                   const ShardLayer& ly, uint64_t pre_mask, int32_t slice_bits,
+                                   int32_t slice, double* state) {
   if (!ctx || !sh || !state) return fail(DTC_EINVAL, "null ctx/shard/state");
   const int k = sh->n_global, nl = sh->n_local;
   if (sh->n_shards != (1 << k) || sh->first_rank != 0)
@@ -2506,7 +2553,7 @@ int dtc_shard_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc
   RunCfg rc = shard_runcfg(pr, nz, sh, seed, traj);
   const Plan& pl = rc.pl;
   const int n_rows = std::max(1, pr->T - 1 + pr->t_offset);
-  if (period < 1 || period > n_rows) return fail(DTC_EINVAL, "period outside kick table");
+  if (ly.row < 0 || ly.row >= n_rows) return fail(DTC_EINVAL, "period outside kick table");
   // the group whose pass goes last carries the exchange (a unitary kick kind,
   // classified on the row that pass actually launches; launch_kick_swap takes
   // 1 <= k <= 6 chunk bits, other shapes run the two calls)
@@ -2517,14 +2564,13 @@ int dtc_shard_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc
   if (fuse) {
     const Group& G = pl.groups[last];
     PassSpec ps{last, no_kick(), no_kick(), dtc::kDiagNone, 0};
-    ps.pre = dtc::KickDesc{1, period - 1, dtc::kKickForward, dtc::kStreamForward,
-                           (uint32_t)period, skip_bits(G, pre_mask)};
+    ps.pre = shard_kick_desc(ly, G, pre_mask);
     const int kind = pass_kind(rc, ps, dtc::kShapeK);
     fuse = kind == dtc::kKindRX || kind == dtc::kKindRY || kind == dtc::kKindGen;
   }
   if (!fuse) {
-    DTC_TRY(dtc_shard_kick_slice(ctx, pr, nz, sh, seed, traj, period, pre_mask, k, slice_bits,
-                                 slice, state));
+    DTC_TRY(shard_kick_slice_impl(ctx, pr, nz, sh, seed, traj, ly, pre_mask, k, slice_bits,
+                                  slice, state));
     return dtc_shard_exchange_slice(ctx, sh, slice_bits, slice, state);
   }
   DTC_HIP(hipSetDevice(ctx->device));
@@ -2539,12 +2585,86 @@ int dtc_shard_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc
     if (!(pre_mask & gb)) continue;
     if (gb & ~low) return fail(DTC_EINVAL, "a site group of the kick mask reaches the slice bits");
     PassSpec ps{(int)g, no_kick(), no_kick(), dtc::kDiagNone, 0};
-    ps.pre = dtc::KickDesc{1, period - 1, dtc::kKickForward, dtc::kStreamForward,
-                           (uint32_t)period, skip_bits(G, pre_mask)};
+    ps.pre = shard_kick_desc(ly, G, pre_mask);
     DTC_TRY(launch_pass_spec(ctx, rc, 0, n_pieces, ps, base, base, dtc::kMeasNone, 1, 2, nullptr,
                              0, nullptr, 0, 0, nullptr, (int)g == last ? k : 0));
   }
   return DTC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dtc_shard_step(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                   const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t inst,
+                   int32_t period, uint64_t pre_mask, int32_t diag, uint64_t post_mask,
+                   const double* src, double* dst, double* obs) {
+  return shard_step_impl(ctx, pr, nz, sh, seed, traj, inst, shard_forward_layers(period),
+                         pre_mask, diag, post_mask, src, dst, obs, false);
+}
+
+int dtc_shard_step_async(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                         const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t inst,
+                         int32_t period, uint64_t pre_mask, int32_t diag, uint64_t post_mask,
+                         const double* src, double* dst, double* obs_dev) {
+  return shard_step_impl(ctx, pr, nz, sh, seed, traj, inst, shard_forward_layers(period),
+                         pre_mask, diag, post_mask, src, dst, obs_dev, true);
+}
+
+int dtc_shard_echo_step(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                        const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t inst,
+                        int32_t t, int32_t k, uint64_t pre_mask, int32_t diag,
+                        uint64_t post_mask, const double* src, double* dst, double* obs) {
+  return shard_echo_step_impl(ctx, pr, nz, sh, seed, traj, inst, t, k, pre_mask, diag, post_mask,
+                              src, dst, obs, false);
+}
+
+int dtc_shard_echo_step_async(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                              const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t inst,
+                              int32_t t, int32_t k, uint64_t pre_mask, int32_t diag,
+                              uint64_t post_mask, const double* src, double* dst,
+                              double* obs_dev) {
+  return shard_echo_step_impl(ctx, pr, nz, sh, seed, traj, inst, t, k, pre_mask, diag, post_mask,
+                              src, dst, obs_dev, true);
+}
+
+int dtc_shard_kick_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                         const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t period,
+                         uint64_t pre_mask, int32_t chunk_bits, int32_t slice_bits, int32_t slice,
+                         double* state) {
+  return shard_kick_slice_impl(ctx, pr, nz, sh, seed, traj, shard_forward_layer(period), pre_mask,
+                               chunk_bits, slice_bits, slice, state);
+}
+
+int dtc_shard_echo_kick_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                              const dtc_shard* sh, uint64_t seed, int64_t traj, int32_t t,
+                              int32_t k, uint64_t pre_mask, int32_t chunk_bits,
+                              int32_t slice_bits, int32_t slice, double* state) {
+  if (!ctx) return fail(DTC_EINVAL, "null ctx");
+  DTC_TRY(shard_echo_check(pr, t, k));
+  return shard_kick_slice_impl(ctx, pr, nz, sh, seed, traj,
+                               shard_echo_layer(t, t + pr->t_offset, k), pre_mask, chunk_bits,
+                               slice_bits, slice, state);
+}
+
+int dtc_shard_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                                  const dtc_shard* sh, uint64_t seed, int64_t traj,
+                                  int32_t period, uint64_t pre_mask, int32_t slice_bits,
+                                  int32_t slice, double* state) {
+  return shard_kick_exchange_slice_impl(ctx, pr, nz, sh, seed, traj, shard_forward_layer(period),
+                                        pre_mask, slice_bits, slice, state);
+}
+
+int dtc_shard_echo_kick_exchange_slice(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz,
+                                       const dtc_shard* sh, uint64_t seed, int64_t traj,
+                                       int32_t t, int32_t k, uint64_t pre_mask,
+                                       int32_t slice_bits, int32_t slice, double* state) {
+  if (!ctx) return fail(DTC_EINVAL, "null ctx");
+  DTC_TRY(shard_echo_check(pr, t, k));
+  return shard_kick_exchange_slice_impl(ctx, pr, nz, sh, seed, traj,
+                                        shard_echo_layer(t, t + pr->t_offset, k), pre_mask,
+                                        slice_bits, slice, state);
 }
 
 int dtc_shard_exchange_slice(dtc_ctx* ctx, const dtc_shard* sh, int32_t slice_bits,

@@ -1694,6 +1694,14 @@ __global__ __launch_bounds__(kThreads, 3) void dtc_kick_final(PassArgs A) {
   pass_body<kShapeK, NIBS, KIND, 1, true, true, false, GEO>(A);
 }
 #undef DTC_DEFINE_FINAL
+// The end of an echo chain on a sharded state (dtc_shard_echo_step, dst ==
+// NULL): the last inverse kick layer on the bits the exchange made local,
+// then (norm, z_q) of every physical bit, no store.  dtc_kick_pass<.., 2>
+// without its stores: the same sums bit for bit, 16 B per amplitude.
+template <int NIBS, int KIND>
+__global__ __launch_bounds__(kThreads, 2) void dtc_kick_sites_final(PassArgs A) {
+  pass_body<kShapeK, NIBS, KIND, 2, true>(A);
+}
 // The energy sweep's last pass (one kick layer past the last period, for the
 // X of its group at the last time point): measures, stores nothing.
 template <int NIBS, int KIND>
@@ -1739,6 +1747,13 @@ hipError_t launch_shape(const PassArgs& a, dim3 grid, int shape, hipStream_t str
     if constexpr (MC == 3) {
       if (shape != kShapeK) return hipErrorInvalidValue;
       hipLaunchKernelGGL((dtc_kick_xfinal<NIBS, KIND>), grid, block, 0, stream, a);
+      return hipGetLastError();
+    } else if constexpr (MC == 2 && GEO == kGeoStd &&
+                         (KIND == kKindRX || KIND == kKindRY || KIND == kKindGen)) {
+      // the end of a sharded echo chain: a kick-only pass, per-site sums at its end
+      if (shape != kShapeK || a.meas != kMeasSites || !a.meas_at_end || a.dst2 || a.basis)
+        return hipErrorInvalidValue;
+      hipLaunchKernelGGL((dtc_kick_sites_final<NIBS, KIND>), grid, block, 0, stream, a);
       return hipGetLastError();
     } else if constexpr (MC != 1) {
       return hipErrorInvalidValue;  // probe passes end an echo chain, energy sweeps a kick pass

@@ -647,6 +647,62 @@ class DtcEngine:
             ctypes.c_int32(period), ctypes.c_uint64(pre_mask), ctypes.c_int32(slice_bits),
             ctypes.c_int32(slice_), ctypes.c_void_p(state_ptr)))
 
+    # -- the echo on a sharded state: layer k of chain t in place of `period` --
+    def shard_echo_step(self, spec: SweepSpec, shard, t: int, k: int, pre_mask: int, diag: bool,
+                        post_mask: int, src_ptr: int, dst_ptr: int | None,
+                        want_obs: bool = False, seed: int = 0x5EED0001, traj: int = 0,
+                        inst: int = 0):
+        """dst = L_{k+1}[post] . (D*)^diag . L_k[pre] . src on every shard held
+        (dtc_shard_echo_step: L_0 undoes the forward layer that ran ahead, L_k
+        is the inverse kick K'_k of chain t); returns obs or None.  ``dst_ptr``
+        None: the chain's measure-only end (needs ``want_obs``)."""
+        obs = np.zeros((shard.n_shards, 1 + shard.n_local)) if want_obs else None
+        _capi.check(self._lib.dtc_shard_echo_step(
+            self._ctx, ctypes.byref(self._problem(spec)), ctypes.byref(self._noise(spec)),
+            ctypes.byref(shard), ctypes.c_uint64(seed), ctypes.c_int64(traj),
+            ctypes.c_int32(inst), ctypes.c_int32(t), ctypes.c_int32(k),
+            ctypes.c_uint64(pre_mask), ctypes.c_int32(int(bool(diag))),
+            ctypes.c_uint64(post_mask), ctypes.c_void_p(src_ptr),
+            ctypes.c_void_p(dst_ptr) if dst_ptr else None, _capi.as_dptr(obs)))
+        return obs
+
+    def shard_echo_step_async(self, spec: SweepSpec, shard, t: int, k: int, pre_mask: int,
+                              diag: bool, post_mask: int, src_ptr: int, dst_ptr: int | None,
+                              obs_ptr: int | None = None, seed: int = 0x5EED0001,
+                              traj: int = 0, inst: int = 0):
+        """shard_echo_step enqueued on the engine stream without waiting
+        (dtc_shard_echo_step_async); obs_ptr is a device array."""
+        _capi.check(self._lib.dtc_shard_echo_step_async(
+            self._ctx, ctypes.byref(self._problem(spec)), ctypes.byref(self._noise(spec)),
+            ctypes.byref(shard), ctypes.c_uint64(seed), ctypes.c_int64(traj),
+            ctypes.c_int32(inst), ctypes.c_int32(t), ctypes.c_int32(k),
+            ctypes.c_uint64(pre_mask), ctypes.c_int32(int(bool(diag))),
+            ctypes.c_uint64(post_mask), ctypes.c_void_p(src_ptr),
+            ctypes.c_void_p(dst_ptr) if dst_ptr else None,
+            ctypes.c_void_p(obs_ptr) if obs_ptr else None))
+
+    def shard_echo_kick_slice(self, spec: SweepSpec, shard, t: int, k: int, pre_mask: int,
+                              chunk_bits: int, slice_bits: int, slice_: int, state_ptr: int,
+                              seed: int = 0x5EED0001, traj: int = 0):
+        """``shard_kick_slice`` with layer k of chain t (dtc_shard_echo_kick_slice)."""
+        _capi.check(self._lib.dtc_shard_echo_kick_slice(
+            self._ctx, ctypes.byref(self._problem(spec)), ctypes.byref(self._noise(spec)),
+            ctypes.byref(shard), ctypes.c_uint64(seed), ctypes.c_int64(traj),
+            ctypes.c_int32(t), ctypes.c_int32(k), ctypes.c_uint64(pre_mask),
+            ctypes.c_int32(chunk_bits), ctypes.c_int32(slice_bits), ctypes.c_int32(slice_),
+            ctypes.c_void_p(state_ptr)))
+
+    def shard_echo_kick_exchange_slice(self, spec: SweepSpec, shard, t: int, k: int,
+                                       pre_mask: int, slice_bits: int, slice_: int,
+                                       state_ptr: int, seed: int = 0x5EED0001, traj: int = 0):
+        """``shard_kick_exchange_slice`` with layer k of chain t
+        (dtc_shard_echo_kick_exchange_slice)."""
+        _capi.check(self._lib.dtc_shard_echo_kick_exchange_slice(
+            self._ctx, ctypes.byref(self._problem(spec)), ctypes.byref(self._noise(spec)),
+            ctypes.byref(shard), ctypes.c_uint64(seed), ctypes.c_int64(traj),
+            ctypes.c_int32(t), ctypes.c_int32(k), ctypes.c_uint64(pre_mask),
+            ctypes.c_int32(slice_bits), ctypes.c_int32(slice_), ctypes.c_void_p(state_ptr)))
+
     def stream_handle(self) -> int:
         """The engine's hipStream_t (for torch.cuda.ExternalStream)."""
         h = ctypes.c_void_p()

@@ -30,9 +30,23 @@ the layout logic on one GPU).  Per-site <Z_i(t)> come from per-shard
 (norm, z_q) partial sums: rank-bit sites take the shard's sign times its norm;
 one all_reduce of L+1 doubles per period joins the ranks.
 
+The echo (``sharded_autocorr``, ``sharded_autocorr_pipelined``): chain t runs
+p = t + t_offset inverse periods off the forward state after period p,
+
+    E_t = K'_p ... D* K'_2 D* K'_1 D* F_p
+
+each the forward period mirrored -- the fused step after an exchange applies
+K'_k to the top bits, D*, and K'_{k+1} to the top group; K'_{k+1} on the other
+local bits follows slice by slice; then the exchange -- so an inverse period
+costs a forward period's passes and one all-to-all.  The chain's first step
+reads the forward buffer (which holds K_{p+1} on the top group already: it
+undoes exactly that layer first) and writes the echo buffer, so forking costs
+no copy; its last step kicks the top bits and measures without storing.
+
 Results are the single-device engine's (same RNG contract: noise keyed by
-logical site), checked in tests/test_sharded_cpu.py (numpy stepper, gloo) and
-tests/test_gpu_sharded.py (engine, virtual ranks, vs dtc_autocorr).
+logical site), checked in tests/test_sharded_cpu.py, test_sharded_echo_cpu.py
+(numpy steppers, gloo) and tests/test_gpu_sharded.py, test_gpu_sharded_echo.py
+(engine, virtual ranks, vs dtc_autocorr).
 """
 from __future__ import annotations
 
@@ -211,6 +225,36 @@ class EngineStepper:
         return self.engine.shard_step(spec, layout.to_c(), period, pre, diag, post,
                                       src.data_ptr(), dst.data_ptr(), want_obs, seed, traj, inst)
 
+    # -- the echo twins: layer k of chain t in place of the period (dst None:
+    # the chain's measure-only end) ---------------------------------------------
+    def step_echo(self, spec, layout, seed, traj, inst, t, k, pre, diag, post, src, dst,
+                  want_obs):
+        import torch
+
+        torch.cuda.synchronize()
+        return self.engine.shard_echo_step(spec, layout.to_c(), t, k, pre, diag, post,
+                                           src.data_ptr(),
+                                           dst.data_ptr() if dst is not None else None,
+                                           want_obs, seed, traj, inst)
+
+    def step_echo_async(self, spec, layout, seed, traj, inst, t, k, pre, diag, post, src, dst,
+                        obs_out):
+        self.engine.shard_echo_step_async(spec, layout.to_c(), t, k, pre, diag, post,
+                                          src.data_ptr(),
+                                          dst.data_ptr() if dst is not None else None,
+                                          obs_out.data_ptr() if obs_out is not None else None,
+                                          seed, traj, inst)
+
+    def kick_slice_echo(self, spec, layout, seed, traj, t, k, pre, chunk_bits, slice_bits,
+                        slice_, buf):
+        self.engine.shard_echo_kick_slice(spec, layout.to_c(), t, k, pre, chunk_bits,
+                                          slice_bits, slice_, buf.data_ptr(), seed, traj)
+
+    def kick_exchange_slice_echo(self, spec, layout, seed, traj, t, k, pre, slice_bits, slice_,
+                                 buf):
+        self.engine.shard_echo_kick_exchange_slice(spec, layout.to_c(), t, k, pre, slice_bits,
+                                                   slice_, buf.data_ptr(), seed, traj)
+
 
 # ---- the sweep ----------------------------------------------------------------------
 
@@ -222,6 +266,57 @@ def sharded_forward(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
     ``world`` processes hold 2^n_global / world shards each (1 process: virtual
     ranks; 2^n_global processes: one shard each).  Returns ``zsite`` [T][L]
     (per-site <Z_i(t)>, same meaning as dtc_autocorr's) and ``norm`` [T]."""
+    return _blocking_sweep(stepper, spec, n_global, inst=inst, traj=traj, seed=seed, rank=rank,
+                           world=world, group=group, exchange=exchange, buffers=buffers,
+                           on_period=on_period, echo_times=None)
+
+
+def _echo_times(spec: SweepSpec, echo_times):
+    """The sorted times of the chains to run (None: every t)."""
+    if echo_times is None:
+        return list(range(spec.T))
+    ts = sorted({int(t) for t in echo_times})
+    if ts and (ts[0] < 0 or ts[-1] >= spec.T):
+        raise ValueError("echo_times must lie in [0, T)")
+    return ts
+
+
+def sharded_autocorr(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, traj: int = 0,
+                     seed: int = 0x5EED0001, rank: int = 0, world: int = 1, group=None,
+                     exchange=None, buffers=None, echo_times=None, on_period=None):
+    """``sharded_forward`` plus the echo: after the forward period p = t +
+    t_offset of every t in ``echo_times`` (None: every t) a chain of p inverse
+    periods runs on two buffers of its own,
+
+        E_t = K'_p ... D* K'_2 D* K'_1 D* F_p
+
+    (K'_k: the inverse kick layer of period p - k + 1, draws of stream 1 + t,
+    counter k; D*: the conjugated RZZ/RZ layer), the trajectory of
+    dtc_autocorr's echo chain draw for draw.  An inverse period is a forward
+    one mirrored: the fused step after an exchange (K'_k on the top bits, D*,
+    K'_{k+1} on the top group), K'_{k+1} on the other local bits, the
+    exchange; a last kick-only step applies K'_p to the top bits and measures
+    without storing.  The fork: the forward buffer holds K_{p+1}[post_bits]
+    F_p (the forward runs one kick layer ahead there), so the chain's first
+    step reads it, undoes exactly that layer, and writes the echo buffer -- no
+    copy.  ``buffers``: four (two forward, two echo).
+
+    Returns ``sharded_forward``'s keys plus ``echo`` [T] = (1-p)^6 z_j(init)
+    <Z_j>(E_t), ``echo_zsite`` [T][L] and ``echo_norm`` [T]; rows of times not
+    in ``echo_times`` are 0."""
+    return _blocking_sweep(stepper, spec, n_global, inst=inst, traj=traj, seed=seed, rank=rank,
+                           world=world, group=group, exchange=exchange, buffers=buffers,
+                           on_period=on_period, echo_times=_echo_times(spec, echo_times))
+
+
+def _one_group(groups, mask: int) -> bool:
+    return any(mask & g == mask for g in groups)
+
+
+def _blocking_sweep(stepper, spec, n_global, *, inst, traj, seed, rank, world, group, exchange,
+                    buffers, on_period, echo_times):
+    """The blocking drivers' sweep: the forward periods and, after the period
+    of every t in ``echo_times``, that t's chain of inverse periods."""
     refuse_bond_noise(spec, "the sharded sweep")
     L, T = spec.L, spec.T
     W = 1 << n_global
@@ -232,7 +327,13 @@ def sharded_forward(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
     if exchange is None:
         exchange = (lambda s, d: virtual_exchange(s, d, W)) if world == 1 else \
             (lambda s, d: collective_exchange(s, d, group))
-    A, Bf = buffers if buffers is not None else stepper.alloc(lay)
+    want_echo = echo_times is not None  # (None: the forward alone)
+    echo_times = echo_times or ()
+    if buffers is None:
+        buffers = stepper.alloc(lay, 4) if want_echo else stepper.alloc(lay)
+    if len(buffers) < (4 if want_echo else 2):
+        raise ValueError("need two forward buffers, and two echo buffers for the chains")
+    A, Bf = buffers[:2]
     nl, top, allb = lay.n_local, lay.top_mask, lay.local_mask
     groups = stepper.plan_groups(nl)
     main = next(g for g in groups if (g >> (nl - 1)) & 1)
@@ -240,11 +341,34 @@ def sharded_forward(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
     P = T - 1 + spec.t_offset
     zs = np.zeros((T, L))
     norm = np.zeros(T)
+    ezs = np.zeros((T, L))
+    enorm = np.zeros(T)
 
     def record(t, obs, layout):
         v = _allreduce(z_from_obs(layout, obs), group)
         norm[t] = v[0]
         zs[t] = v[1:]
+
+    def chain(t, p, layout):
+        """E_t from the forward buffer A (after its fused step of period p)."""
+        E1, E2 = buffers[2:4]
+        rest = allb & ~post_bits
+        stepper.step_echo(spec, layout, seed, traj, inst, t, 0, post_bits if p < P else 0, True,
+                          post_bits, A, E1, False)
+        for k in range(1, p + 1):
+            if rest:
+                stepper.step_echo(spec, layout, seed, traj, inst, t, k, rest, False, 0, E1, E1,
+                                  False)
+            exchange(E1, E2)
+            layout = layout.exchanged()
+            if k < p:
+                stepper.step_echo(spec, layout, seed, traj, inst, t, k, top, True, post_bits,
+                                  E2, E1, False)
+        # the end: K'_p on the top bits, measured, never read again
+        obs = stepper.step_echo(spec, layout, seed, traj, inst, t, p, top, False, 0, E2,
+                                None if _one_group(groups, top) else E1, True)
+        v = _allreduce(z_from_obs(layout, obs), group)
+        enorm[t], ezs[t] = v[0], v[1:]
 
     stepper.set_basis(spec, lay, seed, traj, A)
     # the prepared product state (noisy X prep included): z_j(init) of the
@@ -254,6 +378,8 @@ def sharded_forward(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
     zinit = 1.0 if init[1 + spec.probe_site] >= 0 else -1.0
     if spec.t_offset == 0:
         norm[0], zs[0] = init[0], init[1:]
+        if 0 in echo_times:  # no period to invert: the prepared state
+            enorm[0], ezs[0] = init[0], init[1:]
     kicked = 0
     for p in range(1, P + 1):
         pre = allb & ~kicked
@@ -267,10 +393,15 @@ def sharded_forward(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
         kicked = post
         if t >= 0:
             record(t, obs, lay)
+        if t in echo_times:
+            chain(t, p, lay)
         if on_period is not None:
             on_period(p)
     fac = (1.0 - spec.p) ** N_ANCILLA_NOISY_GATES
-    return {"zsite": zs, "norm": norm, "fwd": fac * zinit * zs[:, spec.probe_site]}
+    out = {"zsite": zs, "norm": norm, "fwd": fac * zinit * zs[:, spec.probe_site]}
+    if want_echo:
+        out.update(echo=fac * zinit * ezs[:, spec.probe_site], echo_zsite=ezs, echo_norm=enorm)
+    return out
 
 
 # ---- the pipelined sweep (C5 on the GPU node) -----------------------------------------
@@ -551,6 +682,67 @@ def sharded_forward_pipelined(stepper, spec: SweepSpec, n_global: int, *, inst: 
                                      fuse_kick_exchange=fuse_kick_exchange), group)
 
 
+def sharded_autocorr_pipelined(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0,
+                               traj: int = 0, seed: int = 0x5EED0001, rank: int = 0,
+                               world: int = 1, group=None, buffers=None, echo_times=None,
+                               stats=None, inplace: bool = False,
+                               fuse_kick_exchange: bool = True):
+    """``sharded_forward_pipelined`` plus the echo chains of ``sharded_autocorr``
+    (the production driver): an inverse period runs the forward period's body
+    -- slice kicks, slice transfers, the fused step -- with the chain's layers,
+    so it costs the forward's passes and one all-to-all; every chain ends in
+    one measure-only pass.  All observables go to device arrays read once at
+    the end.
+
+    Buffers: ``(A, B, E1, E2)`` out of place (two forward, two echo).  In place
+    (virtual ranks) ``(A, E)`` -- the fork writes E, any echo times -- or
+    ``(A,)`` alone: the chain then runs in A and consumes the forward state, so
+    only ``echo_times == [T - 1]`` is possible (ValueError otherwise): the
+    L = 34 state on one GPU.
+
+    ``stats`` gains ``echo_period_ms`` (the engine-stream wall of every inverse
+    period, in the order run); the exchange windows list the inverse periods'
+    exchanges in the order run too."""
+    refuse_bond_noise(spec, "the sharded sweep")
+    return _run_rank(_pipelined_rank(stepper, spec, n_global, inst=inst, traj=traj, seed=seed,
+                                     rank=rank, world=world, group=group, buffers=buffers,
+                                     stats=stats, inplace=inplace,
+                                     fuse_kick_exchange=fuse_kick_exchange,
+                                     echo_times=_echo_times(spec, echo_times)), group)
+
+
+class _Layers:
+    """How the pipelined period body addresses its kick layers: the forward's
+    by their period, those of chain ``t`` by their index k."""
+
+    def __init__(self, stepper, spec, seed, traj, inst, t=None):
+        self.s, self.spec, self.seed, self.traj, self.inst, self.t = (stepper, spec, seed, traj,
+                                                                      inst, t)
+        self.fusable = hasattr(stepper, "kick_exchange_slice" if t is None
+                               else "kick_exchange_slice_echo")
+
+    def step(self, lay, idx, pre, diag, post, src, dst, obs_out):
+        a = (self.spec, lay, self.seed, self.traj, self.inst)
+        if self.t is None:
+            self.s.step_async(*a, idx, pre, diag, post, src, dst, obs_out)
+        else:
+            self.s.step_echo_async(*a, self.t, idx, pre, diag, post, src, dst, obs_out)
+
+    def kick_slice(self, lay, idx, pre, chunk_bits, slice_bits, sl, buf):
+        a = (self.spec, lay, self.seed, self.traj)
+        if self.t is None:
+            self.s.kick_slice(*a, idx, pre, chunk_bits, slice_bits, sl, buf)
+        else:
+            self.s.kick_slice_echo(*a, self.t, idx, pre, chunk_bits, slice_bits, sl, buf)
+
+    def kick_exchange_slice(self, lay, idx, pre, slice_bits, sl, buf):
+        a = (self.spec, lay, self.seed, self.traj)
+        if self.t is None:
+            self.s.kick_exchange_slice(*a, idx, pre, slice_bits, sl, buf)
+        else:
+            self.s.kick_exchange_slice_echo(*a, self.t, idx, pre, slice_bits, sl, buf)
+
+
 def _run_rank(gen, group):
     """Drive one rank's generator in its own process: exchange marks are
     no-ops, the join is the process group's all-reduce."""
@@ -603,8 +795,9 @@ def loopback_forward_pipelined(steppers, spec: SweepSpec, n_global: int, *, inst
 def _pipelined_rank(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, traj: int = 0,
                     seed: int = 0x5EED0001, rank: int = 0, world: int = 1, group=None,
                     buffers=None, stats=None, inplace: bool = False,
-                    fuse_kick_exchange: bool = True):
-    """One rank's ``sharded_forward_pipelined`` as a generator: it yields
+                    fuse_kick_exchange: bool = True, echo_times=None):
+    """One rank's ``sharded_forward_pipelined`` (``echo_times`` None) or
+    ``sharded_autocorr_pipelined`` (a list of times) as a generator: it yields
     ("exchange", None) once a period's slice transfers are all posted (before
     waiting for them) and ("allreduce", vec) for the final join, receiving the
     sum.  ``_run_rank`` drives one process's rank (the yields are no-ops, the
@@ -620,14 +813,26 @@ def _pipelined_rank(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
     lay = initial_layout(L, n_global, rank * n_sh, n_sh)
     if inplace and world != 1:
         raise ValueError("the in-place exchange needs every shard in one process (world 1)")
-    if buffers is not None:
-        A, Bf = (tuple(buffers) + (None,))[:2]
-    elif inplace:
-        A, Bf = stepper.alloc(lay, n_buffers=1)[0], None
-    else:
-        A, Bf = stepper.alloc(lay)
+    want_echo = echo_times is not None
+    echo_times = echo_times or ()
+    # forward buffers (A, Bf), echo buffers (E1, E2); in place Bf = A, E2 = E1,
+    # and with no echo buffer at all the one chain runs in A
     if inplace:
-        Bf = A
+        bufs = [b for b in (buffers or ()) if b is not None]
+        if not bufs:
+            bufs = list(stepper.alloc(lay, n_buffers=2 if want_echo else 1))
+        A = Bf = bufs[0]
+        E1 = E2 = bufs[1] if len(bufs) > 1 else A
+        if E1 is A and any(t != T - 1 for t in echo_times):
+            raise ValueError("one buffer holds one chain, after the last period: "
+                             "echo_times must be [T - 1] (or pass an echo buffer too)")
+    else:
+        if buffers is None:
+            buffers = stepper.alloc(lay, n_buffers=4 if want_echo else 2)
+        if len(buffers) < (4 if want_echo else 2):
+            raise ValueError("need two forward buffers, and two echo buffers for the chains")
+        A, Bf = buffers[:2]
+        E1, E2 = buffers[2:4] if want_echo else (None, None)
     nl, top, allb = lay.n_local, lay.top_mask, lay.local_mask
     groups = stepper.plan_groups(nl)
     main = next(g for g in groups if (g >> (nl - 1)) & 1)
@@ -645,54 +850,100 @@ def _pipelined_rank(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
     if inplace and not chunked:
         raise ValueError("the in-place exchange needs chunks of at least one tile")
     P = T - 1 + spec.t_offset
-    fuse_kick = fuse_kick_exchange and hasattr(stepper, "kick_exchange_slice")
     obs = stepper.obs_buffer(P + 1, n_sh, 1 + nl)
+    eobs = stepper.obs_buffer(T, n_sh, 1 + nl) if want_echo else None
     layouts = [lay]
     xch = _SliceExchange(stepper, W, S, rank, world, group, inplace=inplace,
                          slice_bits=slice_bits if chunked else 0)
-    marks = [] if xch.cuda else None  # engine-stream events, one per period boundary
+    # engine-stream events around every period: (start, end, is an inverse period)
+    marks = [] if xch.cuda else None
+    last = [None]
 
-    def mark():
-        if marks is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(xch.eng)
-            marks.append(e)
+    def mark(reuse=False):
+        if marks is None:
+            return None
+        if not (reuse and last[0] is not None):
+            last[0] = torch.cuda.Event(enable_timing=True)
+            last[0].record(xch.eng)
+        return last[0]
 
-    stepper.set_basis(spec, lay, seed, traj, A)
-    stepper.step_async(spec, lay, seed, traj, inst, 1, 0, False, 0, A, A, obs[0])
-    kicked = 0
-    mark()
-    for p in range(1, P + 1):
-        pre = allb & ~kicked
+    def period(ly, idx, lay, pre, src, xdst, dst, diag, post, obs_out):
+        """One period, forward or inverse: layer ``idx`` on the local bits
+        ``pre`` of ``src`` slice by slice, each slice's transfer to ``xdst``
+        behind its kick, then the fused step on the received shard (layer idx
+        on the top bits, the diagonal, layer idx + 1 on ``post``) into ``dst``.
+        Returns the bit map after the exchange."""
+        start = mark(reuse=True)
         if pre & post_bits or not chunked:
             # the first period's top group (its kicks mix the chunks), or every
             # pre-kick when a chunk is smaller than a tile
             whole = pre if not chunked else pre & post_bits
-            stepper.step_async(spec, lay, seed, traj, inst, p, whole, False, 0, A, A, None)
+            ly.step(lay, idx, whole, False, 0, src, src, None)
             pre &= ~whole
         for sl in range(S):
-            if inplace and pre and fuse_kick:
+            if inplace and pre and fuse_kick_exchange and ly.fusable:
                 # one GPU: the slice's last kick pass stores each piece at its
                 # partner's place (the exchange costs no pass of its own)
-                xch.kick_and_swap(sl, lambda: stepper.kick_exchange_slice(
-                    spec, lay, seed, traj, p, pre, slice_bits, sl, A))
+                xch.kick_and_swap(sl, lambda: ly.kick_exchange_slice(lay, idx, pre, slice_bits,
+                                                                     sl, src))
                 continue
             if pre:
-                stepper.kick_slice(spec, lay, seed, traj, p, pre, n_global, slice_bits if chunked
-                                   else 0, sl, A)
-            xch.send(sl, A, Bf, lay)
+                ly.kick_slice(lay, idx, pre, n_global, slice_bits if chunked else 0, sl, src)
+            xch.send(sl, src, xdst, lay)
         yield ("exchange", None)  # every rank's transfers of the period are posted
         xch.finish()
         lay = lay.exchanged()
+        ly.step(lay, idx, top, diag, post, xdst, dst, obs_out)
+        if marks is not None:
+            marks.append((start, mark(), ly.t is not None))
+        return lay
+
+    def chain(t, p, lay):
+        """Chain t off the forward buffer A, which holds K_{p+1}[post_bits] F_p
+        (p < P; F_P at the end): the first step undoes that layer, applies D*
+        and K'_1 on the top group and writes the echo buffer; p inverse periods
+        follow, the last one ending in the measure-only pass."""
+        ly = _Layers(stepper, spec, seed, traj, inst, t)
+        ly.step(lay, 0, post_bits if p < P else 0, True, post_bits, A, E1, None)
+        last[0] = None
+        rest = allb & ~post_bits
+        for k in range(1, p + 1):
+            end = k == p
+            lay = yield from period(ly, k, lay, rest, E1, E2, None if end else E1, not end,
+                                    0 if end else post_bits, eobs[t] if end else None)
+        return lay
+
+    fw = _Layers(stepper, spec, seed, traj, inst)
+    elayouts = {}
+    stepper.set_basis(spec, lay, seed, traj, A)
+    stepper.step_async(spec, lay, seed, traj, inst, 1, 0, False, 0, A, A, obs[0])
+    kicked = 0
+    for p in range(1, P + 1):
         post = post_bits if p < P else 0
-        stepper.step_async(spec, lay, seed, traj, inst, p, top, True, post, Bf, A, obs[p])
+        lay = yield from period(fw, p, lay, allb & ~kicked, A, Bf, A, True, post, obs[p])
         layouts.append(lay)
         kicked = post
-        mark()
+        t = p - spec.t_offset
+        if t in echo_times:
+            elayouts[t] = yield from chain(t, p, lay)
     stepper.synchronize()
-    o = obs.cpu().numpy() if hasattr(obs, "cpu") else np.asarray(obs)
+
+    def host(o):
+        return o.cpu().numpy() if hasattr(o, "cpu") else np.asarray(o)
+
+    o = host(obs)
     z = np.stack([z_from_obs(layouts[p], o[p]) for p in range(P + 1)])
-    z = yield ("allreduce", z)
+    if want_echo:
+        eo = host(eobs)
+        ez = np.zeros((T, 1 + L))
+        for t, elay in elayouts.items():
+            ez[t] = z_from_obs(elay, eo[t])
+        joined = yield ("allreduce", np.concatenate([z, ez]))
+        z, ez = joined[:P + 1], joined[P + 1:]
+        if spec.t_offset == 0 and 0 in echo_times:
+            ez[0] = z[0]  # no period to invert: the prepared state
+    else:
+        z = yield ("allreduce", z)
     zinit = 1.0 if z[0, 1 + spec.probe_site] >= 0 else -1.0
     zs = np.zeros((T, L))
     norm = np.zeros(T)
@@ -705,7 +956,13 @@ def _pipelined_rank(stepper, spec: SweepSpec, n_global: int, *, inst: int = 0, t
         # fused in place: the windows span the slice kicks as well as the swaps
         stats["exchange_ms"] = [] if xch.fused else windows
         stats["kick_exchange_ms"] = windows if xch.fused else []
-        stats["period_ms"] = ([a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:])]
-                              if marks else [])
+        ms = [(a.elapsed_time(b), inv) for a, b, inv in marks] if marks else []
+        stats["period_ms"] = [m for m, inv in ms if not inv]
+        if want_echo:
+            stats["echo_period_ms"] = [m for m, inv in ms if inv]
     fac = (1.0 - spec.p) ** N_ANCILLA_NOISY_GATES
-    return {"zsite": zs, "norm": norm, "fwd": fac * zinit * zs[:, spec.probe_site]}
+    out = {"zsite": zs, "norm": norm, "fwd": fac * zinit * zs[:, spec.probe_site]}
+    if want_echo:
+        out.update(echo=fac * zinit * ez[:, 1 + spec.probe_site], echo_zsite=ez[:, 1:],
+                   echo_norm=ez[:, 0])
+    return out

@@ -130,6 +130,11 @@ def run_sweep(spec: SweepSpec, n_traj: int | None = None, shots: int | None = No
     else:
         out = eng.autocorr(spec, n_traj, seed=seed, traj_offset=traj_offset, want_fwd=want_fwd,
                            want_echo=want_echo, want_zsite=want_zsite, batch=batch)
+    return _sweep_result(spec, out, shots, seed)
+
+
+def _sweep_result(spec: SweepSpec, out: dict, shots, seed) -> SweepResult:
+    """The estimators of the module docstring on per-trajectory values."""
     rng = np.random.default_rng(seed)
     res = {}
     for key in ("fwd", "echo"):
@@ -148,6 +153,47 @@ def run_sweep(spec: SweepSpec, n_traj: int | None = None, shots: int | None = No
             res[key] = _shot_estimate(a, shots, rng)
     return SweepResult(res["fwd"], res["echo"], out.get("fwd"), out.get("echo"),
                        out.get("zsite"))
+
+
+def refuse_state_shards(spec: SweepSpec, independent_t: bool = False) -> None:
+    """What the sharded-state sweep does not take (checked before an engine is
+    opened): device-like noise, bond noise, and the estimators that are not
+    per-trajectory values of one forward sweep."""
+    if spec.device is not None:
+        raise ValueError("a sharded state takes depolarizing or noiseless kicks, not "
+                         "device-like noise")
+    if spec.has_bond_noise:
+        raise ValueError("a sharded state does not take bond noise")
+    if independent_t:
+        raise ValueError("a sharded state runs every t off one forward trajectory "
+                         "(no independent_t)")
+
+
+def run_sharded_state_sweep(spec: SweepSpec, state_shards: int, n_traj: int,
+                            shots: int | None = None, engine: DtcEngine | None = None,
+                            seed: int = 0x5EED0001, traj_offset: int = 0, rank: int = 0,
+                            world: int = 1, group=None) -> SweepResult:
+    """``run_sweep`` with every state split over 2^state_shards shards
+    (sharded.sharded_autocorr_pipelined per (instance, trajectory); the sizes
+    above one device's, L = 33, 34): virtual ranks in one process (world 1), or
+    one shard per rank of a 2^state_shards-rank process group.  Same
+    per-trajectory values and estimators as ``run_sweep``."""
+    from . import sharded
+
+    refuse_state_shards(spec)
+    eng = engine or _default_engine()
+    stepper = sharded.EngineStepper(eng)
+    n_sh = (1 << state_shards) // world
+    bufs = stepper.alloc(sharded.initial_layout(spec.L, state_shards, rank * n_sh, n_sh), 4)
+    out = {"fwd": np.zeros((spec.n_inst, n_traj, spec.T)),
+           "echo": np.zeros((spec.n_inst, n_traj, spec.T))}
+    for i in range(spec.n_inst):
+        for j in range(n_traj):
+            r = sharded.sharded_autocorr_pipelined(stepper, spec, state_shards, inst=i,
+                                                   traj=traj_offset + j, seed=seed, rank=rank,
+                                                   world=world, group=group, buffers=bufs)
+            out["fwd"][i, j], out["echo"][i, j] = r["fwd"], r["echo"]
+    return _sweep_result(spec, out, shots, seed)
 
 
 _ENGINE = None
