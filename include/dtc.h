@@ -518,12 +518,62 @@ int dtc_sample_draws(uint64_t seed, int64_t traj, int32_t p, int32_t basis, int3
 int dtc_sample_state(const double* state, int32_t L, int32_t basis, const double* u, int32_t n,
                      uint64_t* bits);
 
+/* All-pair correlators of the forward sweep (no reference counterpart: the
+ * reference measures the nearest-neighbour terms of H only).  For every
+ * trajectory of dtc_energy and every time t, on the forward state psi after
+ * p = t + t_offset periods (2^L amplitudes, site i = bit i, z_i(y) = +1 / -1 for
+ * bit i of y clear / set):
+ *   z[i]          = sum_y |psi_y|^2 z_i(y)                  <Z_i>
+ *   zz[(i, j)]    = sum_y |psi_y|^2 z_i(y) z_j(y), i < j    <Z_i Z_j>
+ * and x, xx: the same sums on H^(x)L psi, <X_i> and <X_i X_j> (a noiseless
+ * basis change, as dtc_energy measures X).  Pairs are in row-major order (0,1),
+ * (0,2), ..., (L-2,L-1): pair (i, j) is entry i (2L - i - 1) / 2 + j - i - 1.
+ * The sums are not divided by the norm (1 up to rounding: depolarizing or
+ * noiseless kicks only; the Python wrapper refuses device-like and bond noise).
+ * Every sum is linear in |psi><psi|, so the mean over trajectories estimates the
+ * depolarizing channel's exact expectation; the
+ * trajectories are dtc_energy's, trajectory for trajectory (no new draws):
+ * zz[(i, i+1)], z and x are dtc_energy's values up to rounding.
+ *
+ * Row p = 0 is formed on the host from the prepared mask m: z[i] = z_i(m),
+ * zz[(i, j)] = z_i(m) z_j(m), x = xx = 0.
+ *
+ * Rows are bit-identical for any batch size, any split of the trajectories and
+ * either batch layout: every sum is formed in a fixed hierarchy over the
+ * logical index (dtc_corr.hip; DESIGN.md "All-pair correlators").
+ *
+ * The forward runs in dtc_sample's K-D passes; each measured state costs one
+ * extra read per basis (and a small reduce over the chunk partials), the X
+ * basis one basis-change pass per site group before it.  Launches are counted
+ * under DTC_KERNEL_REDUCE when profiling, the read with 16 B per amplitude.
+ *
+ * z, x: [n_inst][n_traj][T][L]; zz, xx: [n_inst][n_traj][T][L (L - 1) / 2]; any may
+ * be NULL (not all): the Z launches run iff z or zz is given, the X-basis
+ * passes and launches iff x or xx is.  Rows t < prob->t_first are left 0;
+ * want_fwd / want_echo ignored.  DTC_EINVAL for a null ctx, all outputs null
+ * and L > 32. */
+int dtc_correlations(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise, uint64_t seed,
+                     int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x,
+                     double* xx);
+/* The same sweep with the per-trajectory rows summed per instance on the device:
+ * z_sum, x_sum [n_inst][T][L], zz_sum, xx_sum [n_inst][T][L (L - 1) / 2] (divide by
+ * n_traj for the means).  Batch-invariant up to rounding only: an instance's
+ * trajectories are added batch by batch. */
+int dtc_correlation_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                         uint64_t seed, int64_t traj_offset, int32_t n_traj, double* z_sum,
+                         double* zz_sum, double* x_sum, double* xx_sum);
+/* host only, the contract's reference: z [L] and zz [L (L - 1) / 2] of a host state of
+ * 2^L complex128 amplitudes; basis 1 applies H^L first.  The chunk partials by
+ * plain loops, combined with the kernels' own index algebra (csrc/dtc_corr.h). */
+int dtc_correlations_state(const double* state, int32_t L, int32_t basis, double* z, double* zz);
+
 /* Profiling: when enabled, every kernel launch is bracketed by HIP events on
  * the ctx stream and accumulated per kernel kind. */
 #define DTC_KERNEL_LO_PASS 0   /* fused RZZ+RZ diagonal + low-site kick pass */
 #define DTC_KERNEL_HI_PASS 1   /* high-site kick pass                        */
 #define DTC_KERNEL_REDUCE 2    /* per-state observable reduction; bond-noise sign pass;
-                                  measurement sampling (weights, picks) */
+                                  measurement sampling (weights, picks); all-pair
+                                  correlators (chunk partials, their reduce) */
 #define DTC_KERNEL_INIT 3      /* preparation: bond-noise diagonal table builder */
 #define DTC_KERNEL_FINAL_PASS 4 /* last pass of an echo chain (sharded ones too): measure, no store */
 #define DTC_KERNEL_EXCHANGE 5  /* virtual ranks' in-place slice exchange        */

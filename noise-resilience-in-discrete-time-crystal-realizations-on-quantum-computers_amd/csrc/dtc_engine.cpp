@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/dtc.h"
+#include "dtc_corr.h"
 #include "dtc_kernels.h"
 #include "dtc_rng.h"
 #include "dtc_schedule.h"
@@ -94,6 +95,9 @@ struct dtc_ctx {
   // measurement sampling (dtc_sample): the chunk weights of the state being
   // sampled, [batch][n_tiles], and the batch's outcomes, z | x
   DevBuf sample_w, sample_bits;
+  // all-pair correlators (dtc_correlations): the chunk partials of the state
+  // being measured, [batch][n_tiles][79]
+  DevBuf corr_part;
   std::vector<dtc::PassKick> pk_host;   // staged pass list (alive until the stream syncs)
   // forward prefix (dtc_prefix_build): every trajectory's state after
   // prefix_periods periods, and what it was built from
@@ -993,6 +997,7 @@ int dtc_close(dtc_ctx* ctx) {
   release(ctx->bond_ang);
   release(ctx->sample_w);
   release(ctx->sample_bits);
+  release(ctx->corr_part);
   for (auto& e : ctx->shard_cache) release(e.diag);
   for (auto& e : ctx->shard_maps) release(e.diag);
   release(ctx->shard_kick);
@@ -1016,6 +1021,7 @@ int dtc_release_buffers(dtc_ctx* ctx) {
   release(ctx->bond_diag);
   release(ctx->sample_w);
   release(ctx->sample_bits);
+  release(ctx->corr_part);
   return DTC_OK;
 }
 
@@ -2168,6 +2174,224 @@ int dtc_sample_state(const double* state, int32_t L, int32_t basis, const double
     if (!(u[k] >= 0.0 && u[k] < 1.0)) return fail(DTC_EINVAL, "uniforms must lie in [0, 1)");
     const size_t x = (size_t)(std::upper_bound(cum.begin(), cum.end(), u[k] * W) - cum.begin());
     bits[k] = (uint64_t)(x < N ? x : last);
+  }
+  return DTC_OK;
+}
+
+namespace {
+
+// The two correlator launches on a batch's states `st` (F, or E = H^L F) for
+// time row t of out [batch][T][L + L (L - 1) / 2] (per time: the sites, then
+// the pairs).  Booked under DTC_KERNEL_REDUCE: the chunk kernel with the
+// batch's 16 B per amplitude, the reduce with the chunk partials and its rows.
+int launch_corr(dtc_ctx* ctx, const RunCfg& rc, int batch, const double2* st, int t, double* out) {
+  const int L = rc.pl.L, n_col = L + dtc::corr::n_pairs(L);
+  dtc::CorrArgs A{};
+  A.state = st;
+  A.partial = (double*)ctx->corr_part.p;
+  A.z = out + (size_t)t * n_col;
+  A.zz = A.z + L;
+  A.out_stride = (int64_t)rc.prob->T * n_col;
+  A.L = L;
+  A.L_eff = rc.pl.L_eff;
+  A.octet_bits = rc.octet_bits;
+  A.batch = batch;
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE, 16.0 * (double)rc.pl.len * batch,
+            dtc::launch_corr_chunk(A, ctx->stream));
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE,
+            8.0 * batch * ((double)rc.pl.n_tiles * dtc::corr::kPartial + n_col),
+            dtc::launch_corr_reduce(A, ctx->stream));
+  return DTC_OK;
+}
+
+// Row p = 0 of one trajectory from its prepared mask m: Z_i = z_i(m),
+// C_ij = z_i(m) z_j(m), added to zo [L] and zzo [L (L - 1) / 2] (either may be null).
+void corr_basis_row(uint64_t m, int L, double* zo, double* zzo) {
+  for (int i = 0; i < L; ++i) {
+    if (zo) zo[i] += ((m >> i) & 1ull) ? -1.0 : 1.0;
+    if (!zzo) continue;
+    for (int j = i + 1; j < L; ++j)
+      zzo[dtc::corr::pair_index(L, i, j)] += (((m >> i) ^ (m >> j)) & 1ull) ? -1.0 : 1.0;
+  }
+}
+
+// sums: the outputs are per-instance sums over the trajectories ([n_inst][T][.],
+// dtc_correlation_sums) instead of per-trajectory rows
+int corr_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+              int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x, double* xx,
+              bool sums) {
+  if (!ctx || (!z && !zz && !x && !xx)) return fail(DTC_EINVAL, "null ctx/outputs");
+  DTC_TRY(check_problem(pr, nz));
+  RunCfg rc;
+  DTC_TRY(init_run_cfg(ctx, pr, nz, nullptr, nullptr, seed, traj_offset, n_traj, false, rc));
+  const Plan& pl = rc.pl;
+  const int T = pr->T, L = pr->L;
+  const int P = T - 1 + pr->t_offset;
+  const int n_pair = dtc::corr::n_pairs(L), n_col = L + n_pair;
+  const int64_t S = (int64_t)pr->n_inst * n_traj;
+  const bool want_z = z || zz, want_x = x || xx;
+  double* const outs[4] = {z, zz, x, xx};
+  const size_t n_rows = (size_t)(sums ? pr->n_inst : S) * T;
+  for (int k = 0; k < 4; ++k)
+    if (outs[k]) std::fill(outs[k], outs[k] + n_rows * ((k & 1) ? n_pair : L), 0.0);
+
+  // Row p = 0: the prepared basis state |m>; every X and XX entry is 0.
+  if (pr->t_offset == 0 && pr->t_first == 0) {
+    for (int64_t s = 0; s < S; ++s) {
+      const uint64_t m = init_state_mask(rc, (uint64_t)(traj_offset + s % n_traj));
+      const size_t r = (size_t)(sums ? s / n_traj : s) * T;
+      corr_basis_row(m, L, z ? z + r * L : nullptr, zz ? zz + r * n_pair : nullptr);
+    }
+  }
+  if (P == 0) return DTC_OK;
+  DTC_TRY(upload_tables(ctx, pr, pl));
+
+  // (the rows of a batch: at most 1 GiB)
+  const size_t row = (size_t)T * n_col;  // values per state and basis
+  const double per_state = (double)pl.len * 16.0 * (want_x ? 2.0 : 1.0);
+  Batch bt;
+  DTC_TRY(plan_batch(ctx, rc, per_state, ctx->F.n + (want_x ? ctx->E.n : 0), false,
+                     std::max<int64_t>(1, (int64_t)((size_t)(1u << 26) / row)), want_x, -1, bt));
+  const int64_t B = bt.B;
+  DTC_TRY(ensure(ctx->corr_part, (size_t)B * pl.n_tiles * dtc::corr::kPartial * sizeof(double)));
+  DTC_TRY(ensure(ctx->vals_f, 2 * (size_t)B * row * sizeof(double)));
+  // per-instance sums: at most (B - 1) / n_traj + 2 instances per batch
+  const int64_t max_inst_b = std::min<int64_t>(pr->n_inst, (B - 1) / n_traj + 2);
+  const size_t n_host = (size_t)(sums ? max_inst_b : B) * row;  // per basis
+  if (sums) DTC_TRY(ensure(ctx->vals_e, 2 * n_host * sizeof(double)));
+  DTC_TRY(ensure_host(ctx->host_f, 2 * n_host));
+  double* const hv = ctx->host_f.p;
+  std::vector<int64_t> masks(B);
+
+  // the schedule (build_sample_schedule, dtc_schedule.h) is the same for every
+  // batch; the state a pass leaves at a time is measured in Z on F, in X on
+  // E = H^L F
+  double2* const F = (double2*)ctx->F.p;
+  double* const zv = (double*)ctx->vals_f.p;
+  double* const xv = zv + (size_t)B * row;
+  std::vector<Launch> sched = build_sample_schedule(rc, F);
+  // rows the device does not write (t < t_first, and p = 0, formed above)
+  const int t0 = std::max(pr->t_first, pr->t_offset == 0 ? 1 : 0);
+
+  for (int64_t bs = 0; bs < S; bs += B) {
+    const int nb = (int)std::min<int64_t>(B, S - bs);
+    DTC_TRY(batch_masks(ctx, rc, bs, nb, masks));
+    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, bt.octet));
+    DTC_HIP(hipMemsetAsync(zv, 0, 2 * (size_t)B * row * sizeof(double), ctx->stream));
+    const AfterLaunch measure = [&](const Launch& l) -> int {
+      if (want_z) DTC_TRY(launch_corr(ctx, rc, nb, F, l.t_state, zv));
+      if (!want_x) return DTC_OK;
+      double2* E = (double2*)ctx->E.p;
+      DTC_TRY(launch_xbasis(ctx, rc, bs, nb, F, E, false));
+      return launch_corr(ctx, rc, nb, E, l.t_state, xv);
+    };
+    DTC_TRY(run_launches(ctx, rc, bs, nb, sched, measure));
+    // the batch's rows, or their sums per instance (traj_sum_kernel), per basis
+    const int64_t i0 = bs / n_traj, n_ib = (bs + nb - 1) / n_traj - i0 + 1;
+    const size_t n_get = (size_t)(sums ? n_ib : nb) * row;
+    for (int k = 0; k < 2; ++k) {
+      if (!(k == 0 ? want_z : want_x)) continue;
+      const double* src = k == 0 ? zv : xv;
+      if (sums) {
+        double* dsum = (double*)ctx->vals_e.p + (size_t)k * n_host;
+        DTC_HIP(dtc::launch_traj_sum(src, nb, (int)row, bs, n_traj, dsum, ctx->stream));
+        src = dsum;
+      }
+      DTC_HIP(hipMemcpyAsync(hv + (size_t)k * n_host, src, n_get * sizeof(double),
+                             hipMemcpyDeviceToHost, ctx->stream));
+    }
+    DTC_HIP(hipStreamSynchronize(ctx->stream));
+    DTC_TRY(settle_pending(ctx));
+    const int64_t n_r = sums ? n_ib : nb, r0 = sums ? i0 : bs;
+    for (int k = 0; k < 2; ++k) {
+      double* const so = outs[2 * k];       // sites
+      double* const po = outs[2 * k + 1];   // pairs
+      if (!so && !po) continue;
+      for (int64_t r = 0; r < n_r; ++r)
+        for (int t = t0; t < T; ++t) {
+          const double* v = hv + (size_t)k * n_host + ((size_t)r * T + t) * n_col;
+          const size_t o = (size_t)(r0 + r) * T + t;
+          // (sums: an instance's trajectories may span batches)
+          if (so)
+            for (int i = 0; i < L; ++i) so[o * L + i] += v[i];
+          if (po)
+            for (int i = 0; i < n_pair; ++i) po[o * n_pair + i] += v[L + i];
+        }
+    }
+  }
+  return DTC_OK;
+}
+
+}  // namespace
+
+int dtc_correlations(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+                     int64_t traj_offset, int32_t n_traj, double* z, double* zz, double* x,
+                     double* xx) {
+  return corr_impl(ctx, pr, nz, seed, traj_offset, n_traj, z, zz, x, xx, false);
+}
+
+int dtc_correlation_sums(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+                         int64_t traj_offset, int32_t n_traj, double* z_sum, double* zz_sum,
+                         double* x_sum, double* xx_sum) {
+  return corr_impl(ctx, pr, nz, seed, traj_offset, n_traj, z_sum, zz_sum, x_sum, xx_sum, true);
+}
+
+int dtc_correlations_state(const double* state, int32_t L, int32_t basis, double* z, double* zz) {
+  namespace cr = dtc::corr;
+  if (!state || !z || (!zz && L > 1)) return fail(DTC_EINVAL, "null argument");
+  if (L < 1 || L > 32) return fail(DTC_EINVAL, "L must be in [1, 32]");
+  if (basis < 0 || basis > 1) return fail(DTC_EINVAL, "basis 0 or 1");
+  const size_t N = (size_t)1 << L;
+  const int L_eff = std::max<int>(L, cr::kChunkBits);
+  const size_t chunk = (size_t)1 << cr::kChunkBits, n_chunks = (size_t)1 << (L_eff - cr::kChunkBits);
+  std::vector<double> w(chunk * n_chunks, 0.0);  // |a|^2, the padding of L < 12 is 0
+  if (basis == 0) {
+    for (size_t y = 0; y < N; ++y)
+      w[y] = state[2 * y] * state[2 * y] + state[2 * y + 1] * state[2 * y + 1];
+  } else {
+    // H on every site: Walsh-Hadamard butterflies, one factor 2^(-L/2) at the end
+    std::vector<double> a(state, state + 2 * N);
+    for (size_t h = 1; h < N; h <<= 1)
+      for (size_t i = 0; i < N; i += 2 * h)
+        for (size_t j = i; j < i + h; ++j)
+          for (int c = 0; c < 2; ++c) {
+            const double p0 = a[2 * j + c], p1 = a[2 * (j + h) + c];
+            a[2 * j + c] = p0 + p1;
+            a[2 * (j + h) + c] = p0 - p1;
+          }
+    const double f = std::ldexp(1.0, -L);
+    for (size_t y = 0; y < N; ++y) w[y] = f * (a[2 * y] * a[2 * y] + a[2 * y + 1] * a[2 * y + 1]);
+  }
+  // the chunk partials as the chunk kernel splits them: per wave (chunk bits 6,
+  // 7) the kept coefficients of the other ten bits by plain loops, then the four
+  // waves combined
+  std::vector<double> part(n_chunks * cr::kPartial);
+  for (size_t c = 0; c < n_chunks; ++c) {
+    double sv[4][cr::kWaveSlots];
+    for (int m = 0; m < (int)chunk; ++m) {
+      const int slot = cr::slot_of_mask(m);
+      if (slot < 0) continue;
+      for (int wv = 0; wv < 4; ++wv) {
+        double acc = 0.0;
+        for (int y = 0; y < (int)chunk; ++y)
+          if (((y >> 6) & 3) == wv)
+            acc += __builtin_parity((unsigned)(y & m)) ? -w[c * chunk + y] : w[c * chunk + y];
+        sv[wv][slot] = acc;
+      }
+    }
+    for (int o = 0; o < cr::kPartial; ++o) {
+      const int m = cr::partial_mask(o);
+      const int slot = cr::slot_of_mask(m & ~cr::kWaveBitMask);
+      part[c * cr::kPartial + o] =
+          cr::wave_combine((m >> 6) & 3, sv[0][slot], sv[1][slot], sv[2][slot], sv[3][slot]);
+    }
+  }
+  const int n_out = L + cr::n_pairs(L);
+  for (int o = 0; o < n_out; ++o) {
+    const cr::Source src = cr::output_source(L, o);
+    double acc = 0.0;
+    for (size_t c = 0; c < n_chunks; ++c) acc += cr::term(&part[c * cr::kPartial], src, c);
+    (o < L ? z[o] : zz[o - L]) = acc;
   }
   return DTC_OK;
 }

@@ -505,4 +505,24 @@ struct SampleArgs {
 hipError_t launch_sample_weights(const SampleArgs& a, hipStream_t stream);
 hipError_t launch_sample_pick(const SampleArgs& a, hipStream_t stream);
 
+// All-pair correlators (dtc_corr.hip, dtc_corr.h; include/dtc.h
+// dtc_correlations): Z_i and C_ij = <Z_i Z_j>, i < j < L, of every state of a
+// batch (of E = H^L F: X_i and <X_i X_j>).  Two launches per batch and basis:
+//  * chunk: one read-only sweep of the batch, the 79 Walsh coefficients of
+//    every chunk's own 12 bits into partial[b][c][79];
+//  * reduce: per (state, output) the chunk partials summed with the signs of
+//    the chunk index's bits, in an order that depends on the chunk index alone,
+//    into z[b * out_stride + i] and zz[b * out_stride + pair].
+struct CorrArgs {
+  const double2* state;    // the batch, in the layout of octet_bits
+  double* partial;         // [batch][2^(L_eff - kTileBits)][79]
+  double* z;               // [batch] rows of L, out_stride apart
+  double* zz;              // [batch] rows of L (L - 1) / 2, out_stride apart
+  int64_t out_stride;
+  int L, L_eff, octet_bits;
+  int batch;
+};
+hipError_t launch_corr_chunk(const CorrArgs& a, hipStream_t stream);
+hipError_t launch_corr_reduce(const CorrArgs& a, hipStream_t stream);
+
 }  // namespace dtc

@@ -193,6 +193,36 @@ def sample_state(psi, L: int, basis: int, u) -> np.ndarray:
     return bits
 
 
+def refuse_correlations(spec: SweepSpec, what: str) -> None:
+    """The all-pair correlators run depolarizing or noiseless kicks only."""
+    if getattr(spec, "device", None) is not None:
+        raise NotImplementedError(
+            f"{what} does not support device-like noise (SweepSpec.device): the correlator "
+            "sweep has no Kraus kick kinds (the sums stay linear there; not built)")
+    if getattr(spec, "has_bond_noise", False):
+        raise NotImplementedError(
+            f"{what} does not support bond noise (SweepSpec.bond_noise): there is no correlator "
+            "entry point taking its per-state diagonal tables")
+
+
+def correlations_state(psi, L: int, basis: int):
+    """Host only (dtc_correlations_state), the correlator contract's reference:
+    ``(z [L], zz [L(L-1)/2])`` of the state ``psi`` (2^L amplitudes, site i = bit
+    i), ``z_i = sum |psi|^2 z_i``, ``zz_(i,j) = sum |psi|^2 z_i z_j`` with the pairs
+    in the order of ``correlations.pair_index``; ``basis`` 1 applies a Hadamard to
+    every site first (X_i, X_i X_j)."""
+    lib = _capi.load_library()
+    buf = np.ascontiguousarray(np.asarray(psi, dtype=np.complex128).reshape(-1))
+    if buf.size != 1 << L:
+        raise ValueError(f"psi must hold 2^L = {1 << L} amplitudes")
+    z = np.zeros(L)
+    zz = np.zeros(L * (L - 1) // 2)
+    _capi.check(lib.dtc_correlations_state(
+        _capi.as_dptr(buf.view(np.float64)), ctypes.c_int32(L), ctypes.c_int32(basis),
+        _capi.as_dptr(z), _capi.as_dptr(zz) if L > 1 else None))
+    return z, zz
+
+
 def bond_struct(p_bond: np.ndarray) -> "_capi.DtcBondNoise":
     b = _capi.DtcBondNoise()
     b.p_bond = _capi.as_dptr(p_bond)
@@ -567,6 +597,47 @@ class DtcEngine:
             out["z"].ctypes.data_as(up) if "z" in out else None,
             out["x"].ctypes.data_as(up) if "x" in out else None))
         return out
+
+    def _correlations(self, fn: str, what: str, spec: SweepSpec, lead: tuple, n_traj: int,
+                      bases: str, seed: int, traj_offset: int, batch: int, t_first: int):
+        refuse_correlations(spec, what)
+        bases = str(bases).lower()
+        if not bases or set(bases) - set("zx"):
+            raise ValueError(f"bases must name 'z', 'x' or both, got {bases!r}")
+        T, L = spec.T, spec.L
+        out = {}
+        for b in "zx":
+            if b in bases:
+                out[b] = np.zeros(lead + (T, L))
+                out[2 * b] = np.zeros(lead + (T, L * (L - 1) // 2))
+        pr = self._problem(spec, True, False, batch, t_first)
+        _capi.check(getattr(self._lib, fn)(
+            self._ctx, ctypes.byref(pr), ctypes.byref(self._noise(spec)), ctypes.c_uint64(seed),
+            ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj),
+            *(_capi.as_dptr(out.get(k)) for k in ("z", "zz", "x", "xx"))))
+        return out
+
+    def correlations(self, spec: SweepSpec, n_traj: int, bases: str = "z",
+                     seed: int = 0x5EED0001, traj_offset: int = 0, batch: int = 0,
+                     t_first: int = 0):
+        """All-pair correlators of the forward sweep (dtc_correlations): for every
+        trajectory of ``energy`` and every time t, ``z`` [n_inst][n_traj][T][L] =
+        <Z_i> and ``zz`` [n_inst][n_traj][T][L(L-1)/2] = <Z_i Z_j>, i < j, in the
+        order of ``correlations.pair_index``; with "x" in ``bases`` also ``x`` and
+        ``xx`` (<X_i>, <X_i X_j>).  Rows before ``t_first`` stay 0.  Depolarizing
+        or noiseless kicks only."""
+        return self._correlations("dtc_correlations", "correlations", spec,
+                                  (spec.n_inst, int(n_traj)), n_traj, bases, seed, traj_offset,
+                                  batch, t_first)
+
+    def correlation_sums(self, spec: SweepSpec, n_traj: int, bases: str = "z",
+                         seed: int = 0x5EED0001, traj_offset: int = 0, batch: int = 0,
+                         t_first: int = 0):
+        """``correlations`` summed over each instance's ``n_traj`` trajectories on
+        the device (dtc_correlation_sums): [n_inst][T][.].  Divide by ``n_traj``
+        for the means."""
+        return self._correlations("dtc_correlation_sums", "correlation_sums", spec,
+                                  (spec.n_inst,), n_traj, bases, seed, traj_offset, batch, t_first)
 
     # -- sharded state (dtc_shard_*; driver: sharded.py) ----------------
     def shard_set_basis(self, spec: SweepSpec, shard, state_ptr: int, seed: int = 0x5EED0001,
