@@ -54,6 +54,18 @@
 #ifndef DTC_WF_WG4
 #define DTC_WF_WG4 1
 #endif
+// Tile 1's program: 0, the three-layout snake 2 -> 1 -> 0 (two LDS re-layouts
+// per kick step); 1, the swap form -- sites 4, 5 and 6, 7 come into registers by
+// row swaps (swap_reg_lane, no LDS), so one re-layout per kick step is left
+// (the layouts and the slot map: dtc_wf_frame.h; the program: dtc_wf_pass).
+// Development A/B, off in the product: the swap form is correct (every
+// wavefront test passes with it, echo within 1.5e-15 of the snake's) and fits
+// four workgroups per CU (118 VGPRs, no more LDS, no scratch), but the 128 row
+// swaps per step cost what the re-layout they replace did: C2 -0.2 % and
+// -0.7 % in two pairs (profiles/r12_wavefront_t1_swap_ab20.txt)
+#ifndef DTC_WF_T1_SWAP
+#define DTC_WF_T1_SWAP 0
+#endif
 
 namespace dtc {
 
@@ -65,14 +77,23 @@ namespace dtc {
 // of dtc_wf_frame.h.  The table is read four entries at a time with their
 // products in between (a scheduling barrier per group), so the sixteen entries
 // are never all live on top of the tile: the pass fits 128 VGPRs.
-template <int LAY>
+// T1Q (layout 0 only): the swap form's layout Q, registers = bits 0..3 as in
+// layout 0 and the same two tables, the thread's tile bits 4..6 from its own map.
+//
+// Layout 0's table sits in LDS in rows of 17 (wf_pad0, dtc_wf_frame.h): a lane
+// reads row (tile bits 4..6) at the register's column, and with rows of 16
+// entries = 256 B the eight rows of a ds_read_b128 lane group fell on the same
+// four banks, an 8-way conflict on every read (SQ_LDS_BANK_CONFLICT: 655 cycles
+// per wave of 2 196 LDS cycles; profiles/r12_wavefront_t1_swap_ab20.txt).
+template <int LAY, bool T1Q = false>
 __device__ __forceinline__ void wf_diag(double2 (&v)[kRegs], const double2* slot, int t,
                                         double2 fac, double2 e) {
-  static_assert(LAY >= 0 && LAY <= 2, "tile layout");
+  static_assert(LAY >= 0 && LAY <= 2 && (!T1Q || LAY == 0), "tile layout");
   const double2 c = cmul(fac, e);
   const double2* tr = slot + (LAY == 1   ? wf_l1_reg_index(ybase<1>(t))
                               : LAY == 2 ? ((t >> 6) & 3)
-                                         : ((t & 7) << 4));
+                              : T1Q      ? wf_pad0(wf_t1_ybase(kWfLayQ, t) & 0x70)
+                                         : wf_pad0((t & 7) << 4));
   constexpr int kStep = LAY == 1 ? 2 : (LAY == 2 ? 4 : 1);
 #pragma unroll
   for (int g = 0; g < kRegs; g += 4) {
@@ -103,11 +124,44 @@ __device__ __forceinline__ void wf_kick_lane3(double2 (&v)[kRegs], double f) {
   }
 }
 
+// The swap form's LDS re-layouts (tile 1, DTC_WF_T1_SWAP): L2s -> Qs, Qs -> L2s
+// and Q -> L2 through the half-tile buffer in exchange_split's discipline --
+// real parts, then imaginary parts, a slot the thread's base XOR a compile-time
+// register offset -- with the slot map of dtc_wf_frame.h, under which every
+// store and load of the three is free of bank conflicts
+// (tools/wavefront_t1_swap_check.cpp).  No barrier before the writes of the
+// first two: the tile is in the same swapped layout whenever it leaves for LDS
+// or comes back, so a thread writes the slots it read itself last.  Q -> L2
+// writes from Q what came back in Qs: the caller puts a barrier in front of it.
+template <int FROM, int TO>
+__device__ __forceinline__ void exchange_t1(double2 (&v)[kRegs], double* s_half, int t) {
+  int bf = wf_t1_slot(wf_t1_ybase(FROM, t)), bt = wf_t1_slot(wf_t1_ybase(TO, t));
+  asm volatile("" : "+v"(bf), "+v"(bt));  // formed afresh per exchange (exchange_split)
+#pragma unroll
+  for (int r = 0; r < kRegs; ++r) s_half[bf ^ wf_t1_slot(wf_t1_roff(FROM, r))] = v[r].x;
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kRegs; ++r) v[r].x = s_half[bt ^ wf_t1_slot(wf_t1_roff(TO, r))];
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kRegs; ++r) s_half[bf ^ wf_t1_slot(wf_t1_roff(FROM, r))] = v[r].y;
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < kRegs; ++r) v[r].y = s_half[bt ^ wf_t1_slot(wf_t1_roff(TO, r))];
+}
+
+// register bits 0, 1 <-> lane bits 4, 5: L2 <-> L2s and Q <-> Qs
+__device__ __forceinline__ void wf_t1_swap(double2 (&v)[kRegs]) {
+  swap_reg_lane<0, 16>(v);
+  swap_reg_lane<1, 32>(v);
+}
+
 // LDS keeps the per-register table of every slot only (dtc_wf_frame.h): 64
-// entries for the even slots and the column tile's odd ones, kWfTabA for tile
-// 1's odd ones.  Slot st's offset, and the whole array, in entries:
+// entries for the even slots and the column tile's odd ones, kWfTabA in rows of
+// 17 (kWfTabA0, wf_diag) for tile 1's odd ones.  Slot st's offset, and the
+// whole array, in entries:
 __host__ __device__ constexpr int wf_slot_ofs(bool two_lay, int st) {
-  return two_lay ? st * kWfTabB : (st >> 1) * kWfTab + (st & 1) * kWfTabB;
+  return two_lay ? st * kWfTabB : (st >> 1) * (kWfTabB + kWfTabA0) + (st & 1) * kWfTabB;
 }
 __host__ __device__ constexpr int wf_tab_lds(bool two_lay) { return wf_slot_ofs(two_lay, kWfSteps + 1); }
 static_assert(kWfTabB == 64 && kWfL1Reg == 64 && kWfTabA == kWfFetchTabA && (kWfSteps & 1) == 0,
@@ -131,9 +185,13 @@ __global__ __launch_bounds__(kThreads, SPLIT ? (wf_wg4(QM0) ? 4 : 3) : 2) void d
   // across lanes (wf_kick_lane3) and the odd steps' diagonals are applied in
   // layout 1 -- two re-layouts per step pair instead of four, all cross-wave.
   constexpr bool kTwoLay = kWfT2Lay1 && QM0 == 8;
+  // Tile 1 in the swap form (DTC_WF_T1_SWAP): layouts L2, L2s, Q, Qs of
+  // dtc_wf_frame.h, the odd slots' diagonals in Q with layout 0's tables
+  constexpr bool kT1Swap = DTC_WF_T1_SWAP != 0 && SPLIT && QM0 == 15;
   // SPLIT: the re-layouts through a half-tile buffer (real parts, then
-  // imaginary parts); with the register tables alone beside it, 39 936 B
-  // (tile 1) and 37 888 B (the column tile): four workgroups fit a CU's LDS
+  // imaginary parts); with the register tables alone beside it, 40 192 B
+  // (tile 1, its layout-0 tables in rows of 17) and 37 888 B (the column
+  // tile): four workgroups fit a CU's LDS
   __shared__ double2 s_tile[SPLIT ? 1 : kTile];
   __shared__ double s_half[SPLIT ? kHalfSlots : 1];
   // A tile that is to stay at three per CU pads s_tab to the full tables'
@@ -206,12 +264,13 @@ __global__ __launch_bounds__(kThreads, SPLIT ? (wf_wg4(QM0) ? 4 : 3) : 2) void d
   // behind the kicks and re-layouts in between.
   auto wf_fetch = [&](auto lay, int st) {
     constexpr int LAY = decltype(lay)::value;
+    // (layout 0 of the swap form is Q: the same tables, its own thread map)
+    const int yb = (kT1Swap && LAY == 0) ? wf_t1_ybase(kWfLayQ, t) : ybase<LAY>(t);
     double2 e = make_double2(1.0, 0.0);
     if ((A.dmask >> st) & 1) {
       const int fx = (int)(fxd >> (kTileBits * st)) & (kTile - 1);
-      e = tg[st * 2 * kWfTab + wf_thr_fetch(LAY, ybase<LAY>(t), fx)];
-      if (st == last && wf_thr_neg(LAY, ybase<LAY>(t), fzx & (kTile - 1)))
-        e = make_double2(-e.x, -e.y);
+      e = tg[st * 2 * kWfTab + wf_thr_fetch(LAY, yb, fx)];
+      if (st == last && wf_thr_neg(LAY, yb, fzx & (kTile - 1))) e = make_double2(-e.x, -e.y);
     }
     return e;
   };
@@ -229,7 +288,7 @@ __global__ __launch_bounds__(kThreads, SPLIT ? (wf_wg4(QM0) ? 4 : 3) : 2) void d
       const int fx = (int)(fxd >> (kTileBits * st)) & (kTile - 1);
       const int j = t ^ wf_reg_xmask(lay, fx);
       const bool neg = st == last && (__popc(j & wf_reg_zmask(lay, fz)) & 1);
-      s_tab[wf_slot_ofs(kTwoLay, st) + j] =
+      s_tab[wf_slot_ofs(kTwoLay, st) + (lay == 0 ? wf_pad0(j) : j)] =
           neg ? make_double2(-stage[st].x, -stage[st].y) : stage[st];
     }
   }
@@ -244,7 +303,8 @@ __global__ __launch_bounds__(kThreads, SPLIT ? (wf_wg4(QM0) ? 4 : 3) : 2) void d
   // one; past those dmask has no bit)
   auto diag = [&](auto lay, int st, auto nlay, int nx) {
     if ((A.dmask >> st) & 1) {
-      wf_diag<decltype(lay)::value>(v, s_tab + wf_slot_ofs(kTwoLay, st), t, gf, cn);
+      constexpr int LAY = decltype(lay)::value;
+      wf_diag<LAY, kT1Swap && LAY == 0>(v, s_tab + wf_slot_ofs(kTwoLay, st), t, gf, cn);
       gf = make_double2(1.0, 0.0);
     }
     if (nx <= kWfSteps) cn = wf_fetch(nlay, nx);
@@ -254,6 +314,18 @@ __global__ __launch_bounds__(kThreads, SPLIT ? (wf_wg4(QM0) ? 4 : 3) : 2) void d
     if (!(A.mask[st] & (0xFu << (4 * N)))) return;
     const RecScalar R(A.recs + ((int64_t)(st >> 1) * A.batch + b) * kRecPerState);
     apply_nibble<N, KIND, N == 0 ? QM0 : 15, /*FRAME=*/true>(v, R, (st & 1) * kTileBits);
+  };
+  // The swap form's kicks of nibble 1, two sites at a time where a row swap
+  // has them in register bits 0, 1: sites 4, 5 in L2s (H = 0), 6, 7 in Qs
+  // (H = 1).  The nibble runs whole or not at all, as kick() has it: the
+  // frame counts a butterfly on each of its sites (dtc_wf_frame.h).
+  auto kick_pair = [&](auto half, int st) {
+    constexpr int H = decltype(half)::value;
+    if (!(A.mask[st] & 0xF0u)) return;
+    const RecScalar R(A.recs + ((int64_t)(st >> 1) * A.batch + b) * kRecPerState);
+    const int k = (st & 1) * kTileBits + 4 + 2 * H;
+    layer_f<KIND, 2, 0>(v, R.d(k, 3));
+    layer_f<KIND, 2, 1>(v, R.d(k + 1, 3));
   };
   // no flush masks are passed to the re-layouts (the frame's X leaves at the
   // store), so the 1 <-> 0 pair stays inside each wave (DTC_WF_WAVE_XCH)
@@ -275,36 +347,72 @@ __global__ __launch_bounds__(kThreads, SPLIT ? (wf_wg4(QM0) ? 4 : 3) : 2) void d
   // (a bottom-tested loop: rotating a top-tested one would clone the first
   // diagonal in front of it again)
   int st = 0;
+  if constexpr (kT1Swap) {
+    // One re-layout per kick step: even steps run L2 -> L2s | Qs -> Q, odd
+    // ones back, the diagonals in the unswapped L2 and Q.  The swaps always
+    // run, whatever the step's mask (the re-layouts exist in one form each).
+    using H0 = std::integral_constant<int, 0>;
+    using H1 = std::integral_constant<int, 1>;
 #pragma unroll 1
-  do {
-    diag(L2{}, st, LOdd{}, st + 1);
-    if (st < n) {
-      kick(L2{}, st);
-      xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
-      kick(L1{}, st);
-      if constexpr (kTwoLay) {
-        kick3(st);
-      } else {
-        xch_tile<SPLIT, 1, 0, kWaveXch>(v, s_tile, s_half, t);
+    do {
+      diag(L2{}, st, L0{}, st + 1);
+      if (st < n) {
+        kick(L2{}, st);
+        wf_t1_swap(v);
+        kick_pair(H0{}, st);
+        exchange_t1<kWfLayL2s, kWfLayQs>(v, s_half, t);
+        kick_pair(H1{}, st);
+        wf_t1_swap(v);
         kick(L0{}, st);
-      }
-      diag(LOdd{}, st + 1, L2{}, st + 2);
-      if (st + 1 < n) {
-        if constexpr (kTwoLay) {
-          kick3(st + 1);
-          kick(L1{}, st + 1);
-        } else {
+        diag(L0{}, st + 1, L2{}, st + 2);
+        if (st + 1 < n) {
           kick(L0{}, st + 1);
-          xch_tile<SPLIT, 0, 1, kWaveXch>(v, s_tile, s_half, t);
-          kick(L1{}, st + 1);
+          wf_t1_swap(v);
+          kick_pair(H1{}, st + 1);
+          exchange_t1<kWfLayQs, kWfLayL2s>(v, s_half, t);
+          kick_pair(H0{}, st + 1);
+          wf_t1_swap(v);
+          kick(L2{}, st + 1);
         }
-        xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
-        kick(L2{}, st + 1);
       }
+      st += 2;
+    } while (st <= n);
+    if (n & 1) {
+      __syncthreads();  // the writes from Q are not the slots read in Qs
+      exchange_t1<kWfLayQ, kWfLayL2>(v, s_half, t);
     }
-    st += 2;
-  } while (st <= n);
-  if (n & 1) xch_tile<SPLIT, kOddLay, 2>(v, s_tile, s_half, t);
+  } else {
+#pragma unroll 1
+    do {
+      diag(L2{}, st, LOdd{}, st + 1);
+      if (st < n) {
+        kick(L2{}, st);
+        xch_tile<SPLIT, 2, 1>(v, s_tile, s_half, t);
+        kick(L1{}, st);
+        if constexpr (kTwoLay) {
+          kick3(st);
+        } else {
+          xch_tile<SPLIT, 1, 0, kWaveXch>(v, s_tile, s_half, t);
+          kick(L0{}, st);
+        }
+        diag(LOdd{}, st + 1, L2{}, st + 2);
+        if (st + 1 < n) {
+          if constexpr (kTwoLay) {
+            kick3(st + 1);
+            kick(L1{}, st + 1);
+          } else {
+            kick(L0{}, st + 1);
+            xch_tile<SPLIT, 0, 1, kWaveXch>(v, s_tile, s_half, t);
+            kick(L1{}, st + 1);
+          }
+          xch_tile<SPLIT, 1, 2>(v, s_tile, s_half, t);
+          kick(L2{}, st + 1);
+        }
+      }
+      st += 2;
+    } while (st <= n);
+    if (n & 1) xch_tile<SPLIT, kOddLay, 2>(v, s_tile, s_half, t);
+  }
   // a launch without any diagonal: the global factor and the frame's Z here
   // (layout 2: the thread's bits 0..7, the registers' 8..11)
   if (!A.dmask) {
@@ -364,3 +472,8 @@ hipError_t launch_wavefront(const WfArgs& a, int kind, hipStream_t stream) {
 }
 
 }  // namespace dtc
+
+// Build query (a data symbol, read by tests/test_gpu_wavefront_t1_swap.py): 1
+// when tile 1's launches run the swap form
+extern "C" __attribute__((visibility("default"))) const int dtc_wf_t1_swap_form =
+    (DTC_WF_T1_SWAP != 0 && DTC_WF_SPLIT != 0) ? 1 : 0;

@@ -185,5 +185,56 @@ DTC_WF_HD inline int wf_reg_zmask(int lay, int fz) {
   return lay == 2 ? ((fz >> 6) & 63) : (lay == 0 ? (fz & 63) : wf_l1_reg_zmask(fz));
 }
 
+// ---- layout 0's register table in LDS -----------------------------------------
+// The 128-entry table over tile bits 0..6 is read per register at row (tile
+// bits 4..6, the thread's) and column (bits 0..3, the register): entry j sits at
+// wf_pad0(j), rows of 17 entries, kWfTabA0 entries in all.  ds_read_b128 serves
+// 16 lanes per LDS cycle, 64 banks of 4 B: rows of 16 entries (256 B) put a
+// group's eight rows on the same four banks; rows of 17 put them four banks
+// apart (tools/wavefront_t1_swap_check.cpp checks the lane groups).
+DTC_WF_HD constexpr int wf_pad0(int j) { return j + (j >> 4); }
+static constexpr int kWfTabA0 = (wf_pad0(kWfFetchTabA - 1) + 1 + 3) & ~3;  // 136
+
+// ---- tile 1's swap form: four layouts, one LDS re-layout per kick step --------
+// (dtc_wavefront.hip, DTC_WF_T1_SWAP; tools/wavefront_t1_swap_check.cpp runs
+// these maps on the CPU.)  A thread is lane bits l0..5 = t & 63 and wave bits
+// w0,1 = t >> 6; y0..11 are the tile index bits, r0..3 the register bits.
+//   L2  (load / store): r = y8..11,             l0..5 = y0..5,        w = y6,7
+//   L2s = L2 after the row swaps l4 <-> r0, l5 <-> r1:
+//                       r = (y4, y5, y10, y11), l0..3 = y0..3, l4,5 = (y8, y9)
+//   Q                 : r = y0..3,  l0..3 = (y4, y5, y8, y9), l4,5 = (y6, y7),
+//                                                              w = (y10, y11)
+//   Qs  = Q after the same two swaps:
+//                       r = (y6, y7, y2, y3),                  l4,5 = (y0, y1)
+// Sites in registers: 8..11, then 4, 5 in the L2 pair; 0..3, then 6, 7 in the
+// Q pair.  The LDS re-layouts run between the swapped forms (L2s <-> Qs) and,
+// behind a pass with an odd step count, Q -> L2.
+enum { kWfLayL2 = 0, kWfLayL2s = 1, kWfLayQ = 2, kWfLayQs = 3 };
+
+// tile index of thread t's register 0, and register r's offset on top of it
+DTC_WF_HD constexpr int wf_t1_ybase(int lay, int t) {
+  const int l03 = t & 15, l45 = (t >> 4) & 3, w = t >> 6;
+  if (lay == kWfLayL2) return t;
+  if (lay == kWfLayL2s) return l03 | (l45 << 8) | (w << 6);
+  const int q = ((l03 & 3) << 4) | ((l03 >> 2) << 8) | (w << 10);
+  return lay == kWfLayQ ? (q | (l45 << 6)) : (q | l45);
+}
+DTC_WF_HD constexpr int wf_t1_roff(int lay, int r) {
+  if (lay == kWfLayL2) return r << 8;
+  if (lay == kWfLayL2s) return ((r & 3) << 4) | ((r >> 2) << 10);
+  if (lay == kWfLayQ) return r;
+  return ((r & 3) << 6) | ((r >> 2) << 2);
+}
+// The slot of tile index y in the half-tile buffer (8-B slots), linear over
+// XOR as slot_add is: low slot bits (y0^y4, y1^y5, y2^y8, y3^y9, y4^y8), the
+// rest y5..y11.  A 16-lane group of a store (l0..3) must differ in slot bits
+// 0..3 and a 32-lane group of a load (l0..4) in bits 0..4 to be free of bank
+// conflicts (8-B slots: banks (2 slot) mod 32 and mod 64); this map does both
+// for the lanes of L2 (y0..4), L2s (y0..3, y8) and Q / Qs (y4, y5, y8, y9 and
+// y6 / y0), which slot_add does not (y9 reaches none of its low bits).
+DTC_WF_HD constexpr int wf_t1_slot(int y) {
+  return y ^ ((y >> 4) & 3) ^ (((y >> 8) & 3) << 2) ^ (((y >> 8) & 1) << 4);
+}
+
 }  // namespace dtc
 #undef DTC_WF_HD
