@@ -64,6 +64,23 @@ def test_correlations_L20_both_layouts(pkg, engine):
         _check_traj(a8, spec, 0, tr, 33)
 
 
+@pytest.mark.parametrize("L,pol,state", [(9, "y", "neel"), (14, "x", "vacuum")])
+def test_correlations_octet_layout(pkg, engine, L, pol, state):
+    """One chunk per state (L = 9) and two global bits (L = 14): nine
+    trajectories in one batch run in the octet layout (a full octet and a
+    partial one), in batches of three contiguous; the rows are the same bits,
+    and trajectory 8 (the partial octet's) is the oracle's."""
+    rng = np.random.default_rng(L + 740)
+    hs, phis = random_disorder(rng, L)
+    spec = pkg.energy.energy_spec(L, 3, hs, phis, 0.94, state, noise_prob=0.1, polarization=pol)
+    a9 = engine.correlations(spec, 9, bases="zx", seed=35, batch=0)
+    a3 = engine.correlations(spec, 9, bases="zx", seed=35, batch=3)
+    for k in KEYS:
+        assert np.any(a9[k][:, :, 1:] != 0.0), k
+        assert np.array_equal(a9[k], a3[k]), k
+    _check_traj(a9, spec, 0, 8, 35)
+
+
 def test_correlations_invariance(pkg, engine):
     rng = np.random.default_rng(41)
     L, n = 13, 24

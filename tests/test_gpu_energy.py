@@ -34,6 +34,27 @@ def test_energy_matches_oracle(pkg, engine, L, T, p, state, pol):
             assert np.abs(got["x"][inst, tr] - x).max() < TOL
 
 
+@pytest.mark.parametrize("L,T,state,pol", [(13, 5, "neel", "circular_left"),
+                                           (17, 4, "vacuum", "x")])
+def test_energy_octet_layout_matches_oracle(pkg, engine, L, T, state, pol):
+    """Nine trajectories in one batch run in the octet layout (a full octet and
+    a partial one; 9 + 4 sites with general kicks, 9 + 8 with RX), in batches of
+    one contiguous: the rows are the same bits, and the oracle's for the
+    trajectories 7 and 8 on either side of the octet's edge."""
+    rng = np.random.default_rng(L + 900)
+    hs, phis = random_disorder(rng, L)
+    spec = pkg.energy.energy_spec(L, T, hs, phis, 0.94, state, noise_prob=0.1, polarization=pol)
+    got = engine.energy(spec, 9, seed=23, batch=0)
+    one = engine.energy(spec, 9, seed=23, batch=1)
+    for k in ("z", "zz", "x"):
+        assert np.array_equal(got[k], one[k]), (k, float(np.abs(got[k] - one[k]).max()))
+    for tr in (7, 8):
+        z, zz, x = energy_oracle.trajectory_energy(spec, 0, tr, seed=23)
+        assert np.abs(got["z"][0, tr] - z).max() < TOL
+        assert np.abs(got["zz"][0, tr] - zz).max() < TOL
+        assert np.abs(got["x"][0, tr] - x).max() < TOL
+
+
 @pytest.mark.parametrize("L,state,pol", [(21, "neel", "x"), (20, "vacuum", "x"),
                                          (24, "vacuum", "y")])
 def test_energy_large_matches_oracle(pkg, engine, L, state, pol):

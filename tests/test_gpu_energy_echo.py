@@ -57,6 +57,23 @@ def test_energy_echo_two_and_three_groups(pkg, engine, L, pol, state, T, n):
         _check(got, spec, 0, tr, 5)
 
 
+def test_energy_echo_octet_layout_matches_oracle(pkg, engine):
+    """L = 17 (9 + 8 sites, RY), nine trajectories: one batch runs the octet
+    layout (a full octet and a partial one), batches of one contiguous states;
+    the rows are the same bits, and the oracle's for the trajectories 7 and 8
+    on either side of the octet's edge."""
+    rng = np.random.default_rng(317)
+    L = 17
+    hs, phis = random_disorder(rng, L)
+    spec = pkg.energy.energy_spec(L, 4, hs, phis, 0.94, "neel", noise_prob=0.1, polarization="y")
+    got = engine.energy_echo(spec, 9, seed=27, batch=0)
+    one = engine.energy_echo(spec, 9, seed=27, batch=1)
+    for key in KEYS:
+        assert np.array_equal(got[key], one[key]), (key, float(np.abs(got[key] - one[key]).max()))
+    for tr in (7, 8):
+        _check(got, spec, 0, tr, 27)
+
+
 def _fresh(pkg, monkeypatch, spec, n, env=None, **kw):
     """One energy_echo call on a fresh engine opened with ``env`` set."""
     with monkeypatch.context() as m:

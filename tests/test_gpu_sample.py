@@ -76,6 +76,22 @@ def test_sample_L20_both_layouts(pkg, engine):
     _check_traj(pkg, a8, spec, 0, 7, 33, 3)
 
 
+@pytest.mark.parametrize("L,pol,state", [(9, "circular_left", "neel"), (14, "y", "vacuum")])
+def test_sample_octet_layout(pkg, engine, L, pol, state):
+    """One tile per state (L = 9) and 10 + 4 sites (L = 14): nine trajectories in
+    one batch run in the octet layout (a full octet and a partial one), in
+    batches of three contiguous; the rows are bit-identical, and trajectory 8
+    (the partial octet's) is the oracle's."""
+    rng = np.random.default_rng(L + 540)
+    hs, phis = random_disorder(rng, L)
+    spec = pkg.energy.energy_spec(L, 4, hs, phis, 0.94, state, noise_prob=0.1, polarization=pol)
+    a9 = engine.sample(spec, 9, n_shots=3, seed=35, batch=0)
+    a3 = engine.sample(spec, 9, n_shots=3, seed=35, batch=3)
+    for b in "zx":
+        assert np.array_equal(a9[b], a3[b]), b
+    _check_traj(pkg, a9, spec, 0, 8, 35, 3)
+
+
 @pytest.mark.parametrize("L,pol,state,T", [(21, "x", "neel", 4), (24, "y", "vacuum", 3)])
 def test_sample_two_and_three_groups(pkg, engine, L, pol, state, T):
     """A further group split (21) and three groups (24): their basis-change passes."""
