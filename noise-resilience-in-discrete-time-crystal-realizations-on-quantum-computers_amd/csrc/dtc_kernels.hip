@@ -718,7 +718,7 @@ struct RoundPlan {
 // kicks still to come act on other sites and commute with it), the Z part at
 // the end of the pass; a pass with A.no_store set stores nothing.
 template <int SHAPE, int NIBS, int KIND, int MC = 0, bool NS = false, bool SPLIT = false,
-          bool DUAL = false, int GEO = kGeoStd, bool XE = false>
+          bool DUAL = false, int GEO = kGeoStd, bool XE = false, bool FRP = false>
 __device__ __forceinline__ void pass_body(const PassArgs& A) {
   using RP = RoundPlan<NIBS, SHAPE>;
   static_assert(!XE || (MC == 3 && !NS && !SPLIT && !DUAL && GEO == kGeoStd &&
@@ -921,14 +921,18 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
   // frames their full-tile re-layouts take the flush barriers and ran 1-2 %
   // slower, r6v / r6w; its dual passes, the 12-site group's and every final
   // pass gain -- dual<7> 9.60 -> 8.62 ms, kdk_final<7> 6.0 -> 5.3, C2 +1.5 %)
+  // FRP: the group's forward K-D-K takes the frame form all the same
+  // (dtc_kdk_pass_fr), so that the forward chain is one arithmetic with and
+  // without dual passes
 #ifdef DTC_FR_ALL_NIBS  // development A/B: frames for the 8-site group's plain passes too
   constexpr bool FR = (KIND == kKindRX || KIND == kKindRY) && MC != 3 && (NIBS == 6 || NIBS == 7) &&
                       GEO == kGeoStd;
 #else
   constexpr bool FR = (KIND == kKindRX || KIND == kKindRY) && MC != 3 &&
-                      (NIBS == 7 || (NIBS == 6 && DUAL)) && GEO == kGeoStd;
+                      (NIBS == 7 || (NIBS == 6 && (DUAL || FRP))) && GEO == kGeoStd;
 #endif
 #endif
+  static_assert(!FRP || FR, "FRP: a plain pass of the 8-site column group in frame form");
   const int fzw = FR ? R.i(kRecTotal, kT12MaskZ) : 0;
   const int fzm = fzw & (kTile - 1);
   // re-layout e's write-side and read-side masks, and the cumulative ones of
@@ -1657,6 +1661,17 @@ template <int NIBS, int KIND, int MC, int GEO = kGeoStd>
 __global__ __launch_bounds__(kThreads, 3) void dtc_kdk_pass3(PassArgs A) {
   pass_body<kShapeKDK, NIBS, KIND, MC, false, true, false, GEO>(A);
 }
+// The 8-site column group's forward K-D-K in Pauli-frame form (pass_body FRP),
+// the form its dual pass runs: the frame's butterflies round differently from
+// the variant branches', and a forward state must not depend on which of its
+// passes started an echo chain (a t_first run starts none before t_first, and
+// its rows are the full run's bits).  The forward chain has one such pass per
+// two periods, so the frame form's slower full-tile re-layouts (above) cost
+// the sweep nothing measurable; the group's echo passes keep the variant form.
+template <int NIBS, int KIND, int MC>
+__global__ __launch_bounds__(kThreads, 2) void dtc_kdk_pass_fr(PassArgs A) {
+  pass_body<kShapeKDK, NIBS, KIND, MC, false, false, false, kGeoStd, false, true>(A);
+}
 // a forward K-D-K that also starts an echo branch (pass_body DUAL): two
 // tiles in registers, so two workgroups per CU; half-tile re-layouts (their
 // opaque per-thread bases keep the addresses out of the register budget: with
@@ -1789,6 +1804,14 @@ hipError_t launch_shape(const PassArgs& a, dim3 grid, int shape, hipStream_t str
       if constexpr (true) {
         if ((a.kdk_split >> (NIBS + (MC >= 2 ? 8 : 0))) & 1) {
           hipLaunchKernelGGL((dtc_kdk_pass3<NIBS, KIND, MC, GEO>), grid, block, 0, stream, a);
+          break;
+        }
+      }
+      if constexpr (NIBS == 6 && (KIND == kKindRX || KIND == kKindRY) && MC <= 1 &&
+                    GEO == kGeoStd) {
+        // the forward chain's passes (D, not D^*): the dual pass's form
+        if (!a.diag_conj) {
+          hipLaunchKernelGGL((dtc_kdk_pass_fr<NIBS, KIND, MC>), grid, block, 0, stream, a);
           break;
         }
       }

@@ -124,6 +124,58 @@ def test_energy_echo_c2_shape(pkg, monkeypatch, n, off, ids):
             assert oinfo["sched"]["folded"] == 0
 
 
+def _c2_wavefront_and_plain(pkg, monkeypatch, spec, n, t_first, seed, states):
+    """An L = 20 call in the octet layout whose chains run the wavefront interior:
+    the oracle's rows for ``states`` ((inst, trajectory) pairs), nothing before
+    ``t_first``, one measure-only end per chain, and the plain interior's rows
+    (DTC_NO_WAVEFRONT=1) within 1e-12.  Returns the rows."""
+    kw = dict(seed=seed, t_first=t_first)
+    got, info = _fresh(pkg, monkeypatch, spec, n, **kw)
+    for inst, tr in states:
+        _check(got, spec, inst, tr, seed, t_first=t_first)
+    for key in KEYS:
+        assert got[key].shape[:3] == (spec.n_inst, n, spec.T)
+        assert not got[key][:, :, :t_first].any()
+        assert got[key][:, :, t_first:].any()
+    assert info["wf"] > 0
+    assert not any(info["lc"].values())
+    assert info["stats"][pkg._capi.KERNEL_FINAL_PASS]["launches"] == spec.T - t_first
+    other, oinfo = _fresh(pkg, monkeypatch, spec, n, env="DTC_NO_WAVEFRONT", **kw)
+    assert oinfo["wf"] == 0
+    for key in KEYS:
+        err = float(np.abs(other[key] - got[key]).max())
+        print(f"DTC_NO_WAVEFRONT {key}: {err:.3e}")
+        assert err < 1e-12, (key, err)
+    return got
+
+
+def test_energy_echo_c2_shape_two_instances(pkg, monkeypatch):
+    """test_energy_echo_c2_shape's sweep with two disorder instances of six
+    trajectories: twelve states, an octet that holds instance 0 and the first two
+    states of instance 1, and a partial octet.  The wavefront pass reads its
+    diagonal tables per instance ((batch_start + b) / n_traj): the oracle's rows
+    for (instance 0, trajectory 5) and (instance 1, trajectory 0), the states on
+    either side of the instance edge, which share an octet."""
+    rng = np.random.default_rng(2021)
+    hs, phis = random_disorder(rng, 20, 2)
+    spec = pkg.SweepSpec(L=20, T=8, hs=hs, phis=phis, g=0.97, noise_prob=0.05)
+    got = _c2_wavefront_and_plain(pkg, monkeypatch, spec, 6, 6, 92, [(0, 5), (1, 0)])
+    # the same trajectory ids under the two instances' angles: other rows
+    for key in KEYS:
+        assert np.abs(got[key][0, :, 6:] - got[key][1, :, 6:]).max() > 1e-3, key
+
+
+def test_energy_echo_c2_shape_ry_neel(pkg, monkeypatch):
+    """The RY twin of test_energy_echo_c2_shape's one-octet case: RY kicks from
+    the Neel state (the wavefront pass's real kicks, tile 1's trailing kick-less
+    diagonal among its passes); the oracle's rows for the trajectories 0 and 7."""
+    rng = np.random.default_rng(2022)
+    hs, phis = random_disorder(rng, 20, 1)
+    spec = pkg.SweepSpec(L=20, T=8, hs=hs, phis=phis, g=0.93, noise_prob=0.05,
+                         polarization="y", initial_state="neel")
+    _c2_wavefront_and_plain(pkg, monkeypatch, spec, 8, 6, 93, [(0, 0), (0, 7)])
+
+
 @pytest.mark.parametrize("L,n", [(20, 3), (21, 8)])
 def test_energy_echo_fallback(pkg, monkeypatch, L, n):
     """No octet layout (3 states) or L = 21: the plain interior, the oracle's rows."""

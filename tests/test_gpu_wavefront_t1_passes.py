@@ -12,8 +12,10 @@ steps (the schedule dump of tools/schedule_check.cpp is asked for exactly that,
 and the engine's launch count must be the dump's); T = 11 at the default cap
 and at caps 2 and 3 (two- and three-step passes, odd and even endings).  No
 schedule of these sizes gives tile 1 a trailing kick-less diagonal (the dump is
-asked for that too): that path is covered on the CPU only
-(tools/wavefront_frame_check.cpp, tools/wavefront_t1_swap_check.cpp).
+asked for that too): with the probe on site 10 it does not occur.  A moved probe
+gives it after 1, 3 and 4 kick steps, and tests/test_gpu_wavefront_inputs.py runs
+those passes on the GPU under RX and RY kicks (the CPU models of that path:
+tools/wavefront_frame_check.cpp, tools/wavefront_t1_swap_check.cpp).
 
 Values: the C oracle per trajectory at 1e-10; the plain interior
 (DTC_NO_WAVEFRONT=1): fwd identical, echo within 1e-12, the project's bound

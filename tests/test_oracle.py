@@ -248,6 +248,42 @@ def test_fused_cpu_restatement_matches_gate_oracle(pkg, L, T, pol, state, toff, 
     assert np.abs(a["echo"] - b["echo"]).max() < 1e-12
 
 
+@pytest.mark.parametrize("L,T,pol,state,toff,probe", [
+    (9, 7, "x", "vacuum", 0, 0),     # the probe on the chain's first site
+    (10, 6, "y", "neel", 1, 9),      # ... on its last, an odd (flipped) one
+    (13, 6, "y", "neel", 1, 11),     # two site groups, the probe in the high one
+    (14, 5, "xy_cycle", "vacuum", 1, 3),
+])
+def test_fused_cpu_restatement_moved_probe_g_list_instances(pkg, L, T, pol, state, toff, probe):
+    """The inputs tests/test_gpu_wavefront_inputs.py takes the fused restatement
+    as its oracle for: a probe away from L / 2, a kick row of its own per period
+    (a g list) and three disorder instances, trajectories from an offset.  Equal
+    to the gate-by-gate oracle per trajectory, and the rows differ between
+    instances and periods (so an oracle that read one instance's angles or one
+    period's row for all would not pass by agreeing with itself)."""
+    rng = np.random.default_rng(100 + L)
+    hs, phis = random_disorder(rng, L, 3)
+    g = list(np.linspace(0.84, 1.0, T - 1 + toff))
+    spec = pkg.SweepSpec(L=L, T=T, hs=hs, phis=phis, g=g, noise_prob=0.07, polarization=pol,
+                         initial_state=state, t_offset=toff, probe_site=probe)
+    assert spec.kick.shape[0] == len(g) and np.abs(spec.kick[0] - spec.kick[-1]).max() > 0.1
+    a = c_oracle.autocorr(spec, 3, seed=5, traj_offset=6)
+    b = c_oracle.autocorr_fused(spec, 3, seed=5, traj_offset=6)
+    for k in ("fwd", "echo"):
+        err = float(np.abs(a[k] - b[k]).max())
+        print(f"L={L} {k}: {err:.3e}")
+        assert err < 1e-12, k
+        assert a[k].shape == (3, 3, T)
+        assert np.abs(a[k][0] - a[k][1]).max() > 1e-3 and np.abs(a[k][1] - a[k][2]).max() > 1e-3
+    # one instance alone gives that instance's rows: the instance index reaches
+    # the angles and nothing else
+    one = pkg.SweepSpec(L=L, T=T, hs=hs[2:3], phis=phis[2:3], g=g, noise_prob=0.07,
+                        polarization=pol, initial_state=state, t_offset=toff, probe_site=probe)
+    c = c_oracle.autocorr_fused(one, 3, seed=5, traj_offset=6)
+    for k in ("fwd", "echo"):
+        assert np.array_equal(c[k][0], b[k][2]), k
+
+
 def test_large_state_sweep_thread_independent(pkg):
     """States of 2^22 amplitudes and more are swept by all threads, one
     trajectory at a time (the L=28 parity runs, test_gpu_l28_oracle.py): the

@@ -13,7 +13,7 @@
 // are the headline line (L = 20, T = 30, x kicks, depolarizing noise, the octet
 // layout, every option at its default).  Keys:
 //   L T t_offset t_first probe n_sub n_pre octet      integers (probe -1: L / 2)
-//   kick=x|y|xy_cycle|gen     noise=none|depol|device|bond|device_bond
+//   kick=x|y|xy_cycle|xy_cycle5|gen     noise=none|depol|device|bond|device_bond
 //   zsite energy want_fwd want_echo                   0 / 1
 //   lightcone lc_wide lc_wide3 dual runahead wavefront split13   0 / 1;  wf_cap
 //   mode=autocorr|energy|sample   energy: build_energy_schedule as energy_impl
@@ -42,13 +42,16 @@ static int usage(const char* what) {
 
 // The kick table of a case: row r, site i, sub-gate q as {re, im} x 4.  x: RX
 // matrices, y: RY (real) matrices, xy_cycle: rows alternate between the two,
-// gen: sub-gate q alternates (a product outside both families).
+// xy_cycle5: five RX rows, five RY rows, ... (the package's xy_cycle kicks:
+// RX for (r / 5) even), gen: sub-gate q alternates (a product outside both
+// families).
 static std::vector<double> kick_table(const std::string& pat, int n_rows, int L, int n_sub) {
   std::vector<double> k((size_t)n_rows * L * n_sub * 8, 0.0);
   for (int r = 0; r < n_rows; ++r)
     for (int i = 0; i < L; ++i)
       for (int q = 0; q < n_sub; ++q) {
-        const bool y = pat == "y" || (pat == "xy_cycle" && (r & 1)) || (pat == "gen" && (q & 1)) ||
+        const bool y = pat == "y" || (pat == "xy_cycle" && (r & 1)) ||
+                       (pat == "xy_cycle5" && ((r / 5) & 1)) || (pat == "gen" && (q & 1)) ||
                        (pat == "gen" && n_sub == 1 && (i & 1));
         const double th = 0.45 + 0.01 * i + 0.003 * r;
         const double c = std::cos(th), s = std::sin(th);
@@ -82,7 +85,8 @@ int main(int argc, char** argv) {
   }
   auto num = [&](const char* k) { return std::atoi(a[k].c_str()); };
   const std::string pat = a["kick"], noise = a["noise"];
-  if (pat != "x" && pat != "y" && pat != "xy_cycle" && pat != "gen") return usage("bad kick");
+  if (pat != "x" && pat != "y" && pat != "xy_cycle" && pat != "xy_cycle5" && pat != "gen")
+    return usage("bad kick");
   if (noise != "none" && noise != "depol" && noise != "device" && noise != "bond" &&
       noise != "device_bond")
     return usage("bad noise");
