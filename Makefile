@@ -29,7 +29,7 @@ LIB     := $(PKG)/lib/libdtc_hip.so
 ORACLE  := oracle/liboracle.so
 ORACLE3 := oracle/liboracle_v3.so
 SRCS    := $(PKG)/csrc/dtc_kernels.hip $(PKG)/csrc/dtc_lightcone.hip $(PKG)/csrc/dtc_tile13.hip $(PKG)/csrc/dtc_bond.hip $(PKG)/csrc/dtc_wavefront.hip $(PKG)/csrc/dtc_sample.hip $(PKG)/csrc/dtc_corr.hip $(PKG)/csrc/dtc_engine.cpp
-HDRS    := $(PKG)/csrc/dtc_kernels.h $(PKG)/csrc/dtc_device.h $(PKG)/csrc/dtc_rng.h $(PKG)/csrc/dtc_wavefront.h $(PKG)/csrc/dtc_wf_frame.h $(PKG)/csrc/dtc_corr.h include/dtc.h
+HDRS    := $(PKG)/csrc/dtc_kernels.h $(PKG)/csrc/dtc_device.h $(PKG)/csrc/dtc_rng.h $(PKG)/csrc/dtc_wavefront.h $(PKG)/csrc/dtc_wf_frame.h $(PKG)/csrc/dtc_pass_frame.h $(PKG)/csrc/dtc_corr.h include/dtc.h
 
 all: $(LIB) $(ORACLE) $(ORACLE3)
 

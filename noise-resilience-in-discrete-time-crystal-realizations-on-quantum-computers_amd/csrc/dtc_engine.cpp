@@ -385,15 +385,13 @@ int launch_pass_spec(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int ba
   A.zx_reg = -1;
   A.zx_lane = -1;
   if (meas_mode == dtc::kMeasEnergy) {
-    // the layout the kernel measures Z, ZZ in (RoundPlan::d_lay, or the IO
-    // layout at the end): its one bond between a register bit and a lane bit
-    const int nibs = ((g.act & 0xF) ? 1 : 0) | ((g.act & 0xF0) ? 2 : 0) | ((g.act & 0xF00) ? 4 : 0);
-    const int io = dtc::io_layout(nibs), o = 3 - io;
-    const bool n0 = nibs & 1, n_o = (nibs >> o) & 1;
+    // the layout the kernel measures Z, ZZ in (the pass program's d_lay, or the
+    // IO layout at the end): its one bond between a register bit and a lane bit
     const bool pre = shape == dtc::kShapeK || shape == dtc::kShapeKD || shape == dtc::kShapeKDK;
+    const bool post = shape == dtc::kShapeDK || shape == dtc::kShapeKDK;
+    const dtc::PassProgram pp = dtc::pass_program(dtc::act_nibs(g.act), pre, post);
     // (an energy echo chain's last pass, kPartXEnd: at its end in layout 2)
-    const int lay = meas_at_end ? ((meas_parts & dtc::kPartXEnd) ? 2 : io)
-                                : (pre ? (n_o ? o : (n0 ? 0 : io)) : io);
+    const int lay = meas_at_end ? ((meas_parts & dtc::kPartXEnd) ? 2 : pp.IO) : pp.d_lay;
     auto tile_bit = [&](int site) {
       return site < g.c ? site : ((site >= g.s && site < g.s + dtc::kTileBits - g.c) ? g.c + site - g.s : -1);
     };
@@ -418,14 +416,12 @@ int launch_pass_spec(dtc_ctx* ctx, const RunCfg& rc, int64_t batch_start, int ba
   }
   if (ps.diag != dtc::kDiagNone && g.tb == dtc::kTileBits && g.c != dtc::kB7Cols) {
     // the kernel's diagonal uses the window table of the register nibble it
-    // is applied in (RoundPlan::d_lay): that nibble must not straddle c
-    // (same rule as RoundPlan: load/store layout IO, other high nibble O)
-    const int nibs = ((g.act & 0xF) ? 1 : 0) | ((g.act & 0xF0) ? 2 : 0) | ((g.act & 0xF00) ? 4 : 0);
-    const int io = dtc::io_layout(nibs), o = 3 - io;
-    const bool n0 = nibs & 1, n_o = (nibs >> o) & 1;
+    // is applied in (the pass program's d_lay; a light-cone pass counts as
+    // one with a pre-kick): that nibble must not straddle c
     const bool pre = shape == dtc::kShapeK || shape == dtc::kShapeKD || shape == dtc::kShapeKDK ||
                      shape == dtc::kShapeLC;
-    const int tb = 4 * (pre ? (n_o ? o : (n0 ? 0 : io)) : io);
+    const bool post = shape == dtc::kShapeDK || shape == dtc::kShapeKDK;
+    const int tb = 4 * dtc::pass_program(dtc::act_nibs(g.act), pre, post).d_lay;
     if (!(tb >= g.c || tb + 4 <= g.c))
       return fail(DTC_EINVAL, "internal: diagonal nibble straddles the column bits");
   }

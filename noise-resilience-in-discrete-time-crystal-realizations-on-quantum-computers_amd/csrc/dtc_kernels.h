@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dtc_pass_frame.h"
+
 namespace dtc {
 
 // Tile geometry: one workgroup owns 2^kTileBits amplitudes of one state,
@@ -23,15 +25,8 @@ static constexpr int kSlotXPre = 8 * kRedLanes;
 static constexpr int kSlotXPost = kSlotXPre + kTileBits;
 static constexpr int kRedSlots = kSlotXPost + kTileBits;
 
-// Load/store register layout of a pass over the register nibbles `nibs`
-// (bit n = nibble n holds active sites): 1 (threads = tile bits 0..3, 8..11:
-// 256-B row segments per 16 lanes) for the nibble sets in DTC_IO1_NIBS, else 2
-// (threads = tile bits 0..7).  Same-box A/B (profiles/r1s_io_ab.json): the
-// 12-site low group of C2 runs 1.60 -> 1.56 ms from layout 1.
-#ifndef DTC_IO1_NIBS
-#define DTC_IO1_NIBS (1 << 7)
-#endif
-constexpr int io_layout(int nibs) { return ((DTC_IO1_NIBS >> nibs) & 1) ? 1 : 2; }
+// (io_layout, the load/store register layout of a pass, and DTC_IO1_NIBS:
+// dtc_pass_frame.h, with the pass program)
 
 enum DiagMode { kDiagNone = 0, kDiagFwd = 1, kDiagConj = 2 };
 // Tile geometries of the 12-bit passes (pass_body GEO): the plan's standard
@@ -201,6 +196,8 @@ enum : int { kT13MaskX1 = 3, kT13MaskX2 = 4, kT13MaskX3 = 5, kT13MaskX4 = 6, kT1
 // the diagonal's Z mask with the frame's extra power of i in bits 16, 17 (i[7])
 static constexpr int kFrameCoef = 3;
 enum : int { kT12MaskX0 = 3, kT12MaskZ = 7, kT12PhShift = 16 };
+static_assert(kT12MaskX0 + kT12Masks == kT12MaskZ && kPassBits == kTileBits,
+              "one mask word per real re-layout (dtc_pass_frame.h), then the Z word");
 
 // One pass's kick layers, as the prep kernel needs them.
 struct PassKick {

@@ -269,50 +269,40 @@ __device__ __forceinline__ void canonicalise(int kind, const double2* m, SiteMat
 __device__ int frame13_records(const PassKick& pk, KickRec* out, const int* fvar, KickRec& tot) {
   constexpr int NB = kMaxTileBits;
   const bool rx = pk.kind == kKindRX;
-  int x = 0, z = 0, ph = 0;
-  auto form_a = [&](int i) { return (fvar[i] >> 1) ^ 1; };
-  auto zbit = [&](int i) { return rx ? (fvar[i] & 1) : ((fvar[i] & 1) ^ form_a(i)); };
+  PauliFrame f;
   auto kick = [&](int h, int q) {
     const int i = h * NB + q;
-    const int fa = form_a(i), n2 = zbit(i);
-    const double g = fa ? -out[i].d[0] : out[i].d[0];
-    const int flip = ((rx ? z : (x ^ z)) >> q) & 1;
-    out[i].d[0] = flip ? -g : g;
+    out[i].d[0] = f.kick(rx, fvar[i], out[i].d[0], q);
     out[i].i[1] = 2;
-    ph += (rx ? 3 * fa : 2 * fa) + 2 * flip;
-    x ^= fa << q;
-    ph += 2 * (n2 & (x >> q) & 1);
-    z ^= n2 << q;
   };
   auto flush_x = [&](int m) {
-    ph += 2 * (__popc(z & m) & 1);
-    x ^= m;
+    f.flush_x(m);
     return m;
   };
   const bool pre = pk.pre.enabled, post = pk.post.enabled;
   auto xbits = [&](int h, int q0, int q1) {
     int m = 0;
-    for (int q = q0; q <= q1; ++q) m |= form_a(h * NB + q) << q;
+    for (int q = q0; q <= q1; ++q) m |= frame_form_a(fvar[h * NB + q]) << q;
     return m;
   };
   int m1 = 0, m2 = 0, m3 = 0, m4 = 0;
   if (pre) {
     for (int q = 4; q <= 8; ++q) kick(0, q);
-    m1 = flush_x(x);
+    m1 = flush_x(f.x);
     for (int q = 0; q <= 3; ++q) kick(0, q);
-    m2 = flush_x(x ^ xbits(0, 9, 12));
+    m2 = flush_x(f.x ^ xbits(0, 9, 12));
     for (int q = 9; q <= 12; ++q) kick(0, q);
   }
   int npost = 0;
   if (post)
-    for (int q = 0; q < NB; ++q) npost |= zbit(NB + q) << q;
-  const int md = z ^ npost;
-  z ^= md;
+    for (int q = 0; q < NB; ++q) npost |= frame_zbit(rx, fvar[NB + q]) << q;
+  const int md = f.z ^ npost;
+  f.z = npost;
   if (post) {
     for (int q = 9; q <= 12; ++q) kick(1, q);
-    m3 = flush_x(x);
+    m3 = flush_x(f.x);
     for (int q = 0; q <= 3; ++q) kick(1, q);
-    m4 = flush_x(x ^ xbits(1, 4, 8));
+    m4 = flush_x(f.x ^ xbits(1, 4, 8));
     kick(1, 8);
     for (int q = 4; q <= 7; ++q) kick(1, q);
   }
@@ -322,101 +312,23 @@ __device__ int frame13_records(const PassKick& pk, KickRec* out, const int* fvar
   tot.i[kT13MaskX3] = m1 ^ m2 ^ m3;
   tot.i[kT13MaskX4] = m1 ^ m2 ^ m3 ^ m4;
   tot.i[kT13MaskZ] = md;
-  return ph;
+  return f.ph;
 }
 
 // The same Pauli-frame records for the 12-bit K-D-K passes of the unitary
-// families (pass_body FR: nibble sets 6 and 7, the standard geometry).  Their
-// program (RoundPlan): pre-kick nibbles IO -> 0 -> O with a re-layout before
-// each but the first, the diagonal, post-kick nibbles O -> 0 -> IO, re-layouts
-// skipped where a layout does not change.  A kick's X is flushed by the first
-// re-layout after it within its half, else (the half's last nibble) by the
-// last one before it; the diagonal flushes Z as in frame13_records (for a
-// pass without one, the global factor's multiply; for a dual pass's echo
-// branch, copied before the diagonal, its own sign flush).  The coefficients
-// go to d[kFrameCoef], the masks and the extra power of i to tot (kT12*).
+// families (pass_body FR: nibble sets 6 and 7, the standard geometry): the
+// walk of dtc_pass_frame.h (frame12_walk, over the program pass_body reads)
+// packed into the records.  The coefficients go to d[kFrameCoef] (d[0], i[1]
+// keep the variant form), the masks and the extra power of i to tot (kT12*).
 __device__ void frame12_records(const PassKick& pk, KickRec* out, const int* fvar, KickRec& tot) {
   constexpr int NT = kTileBits;
-  const bool rx = pk.kind == kKindRX;
-  int nibs = 0;
-  for (int n = 0; n < 3; ++n)
-    if (pk.act & (0xF << (4 * n))) nibs |= 1 << n;
-  const bool pre = pk.pre.enabled, post = pk.post.enabled;
-  const int IO = io_layout(nibs), O = 3 - IO;
-  const bool n0 = nibs & 1, nIO = (nibs >> IO) & 1, nO = (nibs >> O) & 1;
-  const int d_lay = pre ? (nO ? O : (n0 ? 0 : IO)) : IO;
-  const int pO = nO ? O : d_lay, p0 = n0 ? 0 : pO, pIO = nIO ? IO : p0;
-  // the program: nibble kicks (h * 4 + nibble), re-layouts (-1), the diagonal (-2)
-  int ev[12], ne = 0;
-  if (pre) {
-    if (nIO) ev[ne++] = IO;
-    if (n0) { ev[ne++] = -1; ev[ne++] = 0; }
-    if (nO) { ev[ne++] = -1; ev[ne++] = O; }
-  }
-  ev[ne++] = -2;
-  if (post) {
-    if (nO) { if (d_lay != O) ev[ne++] = -1; ev[ne++] = 4 + O; }
-    if (n0) { if (pO != 0) ev[ne++] = -1; ev[ne++] = 4 + 0; }
-    if (nIO) { if (p0 != IO) ev[ne++] = -1; ev[ne++] = 4 + IO; }
-    if (pIO != IO) ev[ne++] = -1;
-  } else if (d_lay != IO) {
-    ev[ne++] = -1;
-  }
-  auto form_a = [&](int i) { return (fvar[i] >> 1) ^ 1; };
-  auto zbit = [&](int i) { return rx ? (fvar[i] & 1) : ((fvar[i] & 1) ^ form_a(i)); };
-  // each kicked nibble's flush: the re-layout it is assigned to, on the read
-  // side when the re-layout follows the kick (the sites are register bits of
-  // its source layout, thread bits of its target: mr), on the write side when
-  // it precedes it (register bits of the target, thread bits of the source:
-  // mw) -- either way the mask stays off the side's register offsets
-  int mw[4] = {0, 0, 0, 0}, mr[4] = {0, 0, 0, 0};
-  {
-    int xi = 0;  // re-layouts seen so far
-    for (int e = 0; e < ne; ++e) {
-      if (ev[e] == -1) ++xi;
-      if (ev[e] < 0) continue;
-      const int h = ev[e] >> 2, nib = ev[e] & 3;
-      // the first re-layout after it within its half, else the last before it
-      int after = -1, k = xi;
-      for (int f = e + 1; f < ne && ev[f] != -2; ++f)
-        if (ev[f] == -1) { after = k; break; }
-      int m = 0;
-      for (int q = 0; q < 4; ++q) m |= form_a(h * NT + 4 * nib + q) << (4 * nib + q);
-      if (after >= 0 && after < 4) mr[after] |= m;
-      else if (after < 0 && xi >= 1 && xi <= 4) mw[xi - 1] |= m;
-    }
-  }
-  int npost = 0;
-  if (post)
-    for (int k = 0; k < NT; ++k)
-      if ((nibs >> (k >> 2)) & 1) npost |= zbit(NT + k) << k;
-  int x = 0, z = 0, ph = 0, xi = 0, md = 0;
-  for (int e = 0; e < ne; ++e) {
-    if (ev[e] == -1) {
-      const int m = xi < 4 ? mw[xi] ^ mr[xi] : 0;
-      ph += 2 * (__popc(z & m) & 1);
-      x ^= m;
-      ++xi;
-    } else if (ev[e] == -2) {
-      md = z ^ npost;
-      z ^= md;
-    } else {
-      const int h = ev[e] >> 2, nib = ev[e] & 3;
-      for (int q = 0; q < 4; ++q) {
-        const int k = 4 * nib + q, i = h * NT + k;
-        const int fa = form_a(i), n2 = zbit(i);
-        const double g = fa ? -out[i].d[0] : out[i].d[0];
-        const int flip = ((rx ? z : (x ^ z)) >> k) & 1;
-        out[i].d[kFrameCoef] = flip ? -g : g;
-        ph += (rx ? 3 * fa : 2 * fa) + 2 * flip;
-        x ^= fa << k;
-        ph += 2 * (n2 & (x >> k) & 1);
-        z ^= n2 << k;
-      }
-    }
-  }
-  for (int e = 0; e < 4; ++e) tot.i[kT12MaskX0 + e] = mw[e] | (mr[e] << 16);
-  tot.i[kT12MaskZ] = md | ((ph & 3) << kT12PhShift);
+  double coef[2 * NT];
+  for (int i = 0; i < 2 * NT; ++i) coef[i] = out[i].d[0];
+  Frame12 fr;
+  frame12_walk(pk.kind == kKindRX, act_nibs(pk.act), pk.pre.enabled, pk.post.enabled, fvar, coef, fr);
+  for (int i = 0; i < 2 * NT; ++i) out[i].d[kFrameCoef] = fr.coef[i];
+  for (int e = 0; e < kT12Masks; ++e) tot.i[kT12MaskX0 + e] = fr.mw[e] | (fr.mr[e] << 16);
+  tot.i[kT12MaskZ] = fr.md | (fr.ph << kT12PhShift);
 }
 
 // The Pauli-frame records of a wavefront launch's row (dtc_wf_frame.h; the
@@ -656,37 +568,38 @@ hipError_t launch_prep(const PrepArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// Compile-time round plan.  NIBS = register nibbles holding active sites
-// (bit n = nibble n).  IO = the load/store layout (io_layout), O = 3 - IO the
-// other high nibble.
+// Compile-time round plan: the pass program of dtc_pass_frame.h for NIBS =
+// register nibbles holding active sites (bit n = nibble n) and the shape's
+// kick layers.  IO = the load/store layout (io_layout), O = 3 - IO the other
+// high nibble.
 // Pre-kick rounds IO -> 0 -> O, diagonal + measurement where the pre-kick
 // ends, post-kick rounds O -> 0 -> IO, store from layout IO.
 template <int NIBS, int SHAPE>
 struct RoundPlan {
-  static constexpr int IO = io_layout(NIBS);
-  static constexpr int O = 3 - IO;
-  static constexpr bool n0 = NIBS & 1, nIO = (NIBS >> IO) & 1, nO = (NIBS >> O) & 1;
   static constexpr bool pre = SHAPE == kShapeK || SHAPE == kShapeKD || SHAPE == kShapeKDK;
   static constexpr bool diag =
       SHAPE == kShapeKD || SHAPE == kShapeDK || SHAPE == kShapeKDK || SHAPE == kShapeD;
   static constexpr bool post = SHAPE == kShapeDK || SHAPE == kShapeKDK;
-  static constexpr int d_lay = pre ? (nO ? O : (n0 ? 0 : IO)) : IO;
-  // layouts reached by the post rounds
-  static constexpr int pO = nO ? O : d_lay;
-  static constexpr int p0 = n0 ? 0 : pO;
-  static constexpr int pIO = nIO ? IO : p0;
-  // Pauli-frame passes: the real re-layouts in program order (their X-flush
-  // masks; frame12_records walks the same sequence): pre IO -> 0 (xA), pre ->
-  // O (xB); post d_lay -> O (x1), -> 0 (x2), -> IO (x3), -> IO (x4); without
-  // a post-kick d_lay -> IO (x5)
-  static constexpr int xA = 0;
-  static constexpr int xB = (pre && n0) ? 1 : 0;
-  static constexpr int npre = (pre && n0 ? 1 : 0) + (pre && nO ? 1 : 0);
-  static constexpr bool r1 = post && nO && d_lay != O;
-  static constexpr bool r2 = post && n0 && pO != 0;
-  static constexpr bool r3 = post && nIO && p0 != IO;
-  static constexpr int x1 = npre, x2 = x1 + (r1 ? 1 : 0), x3 = x2 + (r2 ? 1 : 0),
-                       x4 = x3 + (r3 ? 1 : 0), x5 = npre;
+  static constexpr PassProgram P = pass_program(NIBS, pre, post);
+  static constexpr int IO = P.IO, O = P.O;
+  static constexpr bool n0 = NIBS & 1, nIO = (NIBS >> IO) & 1, nO = (NIBS >> O) & 1;
+  // the layouts behind the pre-kick's nibble-0 round, at the diagonal, and
+  // behind the post rounds
+  static constexpr int k0 = P.k0, d_lay = P.d_lay, pO = P.pO, p0 = P.p0, pIO = P.pIO;
+  // A re-layout site of pass_body names its re-layout: the one in front of
+  // the pre-kick of nibble 0 / O, of the post-kick of nibble O / 0 / IO, or
+  // the one that ends the pass -- integral constants of its index among the
+  // pass's real re-layouts in program order (the mask word of the Pauli-frame
+  // passes, the same sequence frame12_walk assigns the X flushes to), -1 where
+  // the layout does not change.  names<E, F, T>: is that the re-layout F -> T.
+  using XPre0 = std::integral_constant<int, P.before(0, 0)>;
+  using XPreO = std::integral_constant<int, P.before(0, O)>;
+  using XPostO = std::integral_constant<int, P.before(1, O)>;
+  using XPost0 = std::integral_constant<int, P.before(1, 0)>;
+  using XPostIO = std::integral_constant<int, P.before(1, IO)>;
+  using XLast = std::integral_constant<int, P.last()>;
+  template <int E, int F, int T>
+  static constexpr bool names = P.names(E, F, T);
 };
 
 // Development-only phase timing (build with -DDTC_PHASE_TIMING): wave 0 of
@@ -911,7 +824,7 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
   // Pauli-frame kicks (frame12_records): the unitary families' passes over
   // nibble sets 6 and 7 that measure no X in flight run one butterfly per
   // kick; the frame's X bits leave through the re-layouts' write slots
-  // (fxm: mask of re-layout e in program order, RoundPlan::x*), its Z bits
+  // (fxm: mask of re-layout e < kT12Masks in program order), its Z bits
   // through the diagonal (fzm: a sign per amplitude, in the window table and
   // the thread's phase) and its extra power of i through the global factor
 #ifdef DTC_ADD_SLOTS
@@ -946,12 +859,16 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
     for (int k = 0; k <= e; ++k) c ^= fxw(k) ^ fxr(k);
     return c;
   };
-  // re-layout e of the forward tile (RoundPlan::x*)
-  auto xch_f = [&](auto from_tag, auto to_tag, int e) {
+  // the forward tile's re-layout F -> T, the plan's re-layout E (RoundPlan::
+  // XPre0 .. XLast; no layout change: no re-layout, no mask read)
+  auto xch_f = [&](auto from_tag, auto to_tag, auto e_tag) {
     constexpr int F = decltype(from_tag)::value, T = decltype(to_tag)::value;
+    constexpr int E = decltype(e_tag)::value;
+    static_assert(RP::template names<E, F, T>, "the site's re-layout is not the plan's");
     // (the pass's first re-layout has no earlier reads to wait for)
-    xch_tile<SPLIT, F, T>(v, s_tile, s_half, t, fxw(e), fxr(e), fxm(e - 1), fxm(e),
-                          e > 0 && (fxw(e) | fxr(e - 1)) != 0);
+    if constexpr (F != T)
+      xch_tile<SPLIT, F, T>(v, s_tile, s_half, t, fxw(E), fxr(E), fxm(E - 1), fxm(E),
+                            E > 0 && (fxw(E) | fxr(E - 1)) != 0);
   };
   // i^k g
   auto rot_i = [](double2 g, int k) {
@@ -1309,6 +1226,7 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
   using L0 = std::integral_constant<int, 0>;
   using LIO = std::integral_constant<int, RP::IO>;
   using LO = std::integral_constant<int, RP::O>;
+  using DL = std::integral_constant<int, RP::d_lay>;
   if constexpr (RP::pre) {
     double sc = 1.0;
     if constexpr (RP::nIO) {
@@ -1323,7 +1241,7 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
       }
     }
     if constexpr (RP::n0) {
-      xch_f(LIO{}, L0{}, RP::xA);
+      xch_f(LIO{}, L0{}, typename RP::XPre0{});
       if (x_pre) measure_x_pre(L0{}, sc);
       apply_nibble<0, KIND, qm(0), FR>(v, R, 0);
       if (x_pre) sc *= nib_w2(0, 0);
@@ -1335,7 +1253,7 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
       }
     }
     if constexpr (RP::nO) {
-      xch_f(std::integral_constant<int, RP::n0 ? 0 : RP::IO>{}, LO{}, RP::xB);
+      xch_f(std::integral_constant<int, RP::k0>{}, LO{}, typename RP::XPreO{});
       if (x_pre) measure_x_pre(LO{}, sc);
       apply_nibble<RP::O, KIND, qm(RP::O), FR>(v, R, 0);
       if constexpr (XE && SHAPE == kShapeK) {
@@ -1366,6 +1284,14 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
         c ^= (m & 0xFFFF) ^ ((m >> 16) & 0xFFFF);
       }
     return c;
+  };
+  // both tiles' re-layout F -> T together, the plan's re-layout E (as xch_f)
+  auto xch_co = [&](auto from_tag, auto to_tag, auto e_tag) {
+    constexpr int F = decltype(from_tag)::value, T = decltype(to_tag)::value;
+    constexpr int E = decltype(e_tag)::value;
+    static_assert(RP::template names<E, F, T>, "the site's re-layout is not the plan's");
+    if constexpr (F != T)
+      exchange_split2<F, T>(v, w, s_half, s_half2, t, fxm(E - 1), fxm(E), fxm2(E - 1), fxm2(E));
   };
   if constexpr (kCo) {
 #pragma unroll
@@ -1416,7 +1342,6 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
     if constexpr (FR) zflush(std::integral_constant<int, RP::d_lay>{}, v, fzm);
   }
   // ---- diagonal and measurement at d_lay ----
-  using DL = std::integral_constant<int, RP::d_lay>;
   if constexpr (RP::diag) diag_in(DL{}, true);
   if constexpr (MC > 0) {
     if (A.meas != kMeasNone && !A.meas_at_end &&
@@ -1430,25 +1355,21 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
   if constexpr (kCo) {
     static_assert(SPLIT, "co-traversed dual pass: half-tile re-layouts");
     if constexpr (RP::nO) {
-      exchange_split2<RP::d_lay, RP::O>(v, w, s_half, s_half2, t, fxm(RP::x1 - 1), fxm(RP::x1),
-                                     fxm2(RP::x1 - 1), fxm2(RP::x1));
+      xch_co(DL{}, LO{}, typename RP::XPostO{});
       apply_nibble<RP::O, KIND, qm(RP::O), FR>(v, R, kTileBits);
       apply_nibble<RP::O, KIND, qm(RP::O), FR>(w, R2, kTileBits);
     }
     if constexpr (RP::n0) {
-      exchange_split2<RP::pO, 0>(v, w, s_half, s_half2, t, fxm(RP::x2 - 1), fxm(RP::x2),
-                                     fxm2(RP::x2 - 1), fxm2(RP::x2));
+      xch_co(std::integral_constant<int, RP::pO>{}, L0{}, typename RP::XPost0{});
       apply_nibble<0, KIND, qm(0), FR>(v, R, kTileBits);
       apply_nibble<0, KIND, qm(0), FR>(w, R2, kTileBits);
     }
     if constexpr (RP::nIO) {
-      exchange_split2<RP::p0, RP::IO>(v, w, s_half, s_half2, t, fxm(RP::x3 - 1), fxm(RP::x3),
-                                     fxm2(RP::x3 - 1), fxm2(RP::x3));
+      xch_co(std::integral_constant<int, RP::p0>{}, LIO{}, typename RP::XPostIO{});
       apply_nibble<RP::IO, KIND, qm(RP::IO), FR>(v, R, kTileBits);
       apply_nibble<RP::IO, KIND, qm(RP::IO), FR>(w, R2, kTileBits);
     }
-    exchange_split2<RP::pIO, RP::IO>(v, w, s_half, s_half2, t, fxm(RP::x4 - 1), fxm(RP::x4),
-                                     fxm2(RP::x4 - 1), fxm2(RP::x4));
+    xch_co(std::integral_constant<int, RP::pIO>{}, LIO{}, typename RP::XLast{});
     if constexpr (kRho) {
       rho_apply(LIO{}, kTileBits, v, 0);
       rho_apply(LIO{}, kTileBits, w, 1);
@@ -1456,7 +1377,7 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
   } else if constexpr (RP::post) {
     double sc = inv_w2_mid;
     if constexpr (RP::nO) {
-      xch_f(std::integral_constant<int, RP::d_lay>{}, std::integral_constant<int, RP::O>{}, RP::x1);
+      xch_f(DL{}, LO{}, typename RP::XPostO{});
       if (x_post) measure_x_post(LO{}, sc);
       apply_nibble<RP::O, KIND, qm(RP::O), FR>(v, R, kTileBits);
       if (x_post) sc *= nib_w2(RP::O, kTileBits);
@@ -1468,7 +1389,7 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
       }
     }
     if constexpr (RP::n0) {
-      xch_f(std::integral_constant<int, RP::pO>{}, std::integral_constant<int, 0>{}, RP::x2);
+      xch_f(std::integral_constant<int, RP::pO>{}, L0{}, typename RP::XPost0{});
       if (x_post) measure_x_post(L0{}, sc);
       apply_nibble<0, KIND, qm(0), FR>(v, R, kTileBits);
       if (x_post) sc *= nib_w2(0, kTileBits);
@@ -1480,17 +1401,17 @@ __device__ __forceinline__ void pass_body(const PassArgs& A) {
       }
     }
     if constexpr (RP::nIO) {
-      xch_f(std::integral_constant<int, RP::p0>{}, std::integral_constant<int, RP::IO>{}, RP::x3);
+      xch_f(std::integral_constant<int, RP::p0>{}, LIO{}, typename RP::XPostIO{});
       if (x_post) measure_x_post(LIO{}, sc);
       apply_nibble<RP::IO, KIND, qm(RP::IO), FR>(v, R, kTileBits);
       if constexpr (XE) {
         if (x_end) measure_x_end(LIO{}, sc * nib_w2(RP::IO, kTileBits));
       }
     }
-    xch_f(std::integral_constant<int, RP::pIO>{}, std::integral_constant<int, RP::IO>{}, RP::x4);
+    xch_f(std::integral_constant<int, RP::pIO>{}, LIO{}, typename RP::XLast{});
     if constexpr (kRho) rho_apply(LIO{}, kTileBits, v, 0);
   } else {
-    xch_f(std::integral_constant<int, RP::d_lay>{}, std::integral_constant<int, RP::IO>{}, RP::x5);
+    xch_f(DL{}, LIO{}, typename RP::XLast{});
   }
   if constexpr (MC > 0) {
     if constexpr (XE) {
@@ -2110,7 +2031,7 @@ __global__ __launch_bounds__(kThreads, 2) void dtc_kick_swap_pass(PassArgs A, in
       apply_nibble<0, KIND>(u, R, 0);
     }
     if constexpr (RP::nO) {
-      exchange<RP::n0 ? 0 : RP::IO, RP::O>(u, s_tile, t);
+      exchange<RP::k0, RP::O>(u, s_tile, t);
       apply_nibble<RP::O, KIND>(u, R, 0);
     }
 #pragma unroll

@@ -14,7 +14,7 @@
 // read at index y ^ x -- the kernel stages its per-workgroup tables with that
 // XOR.  Z commutes with the diagonals; it leaves as a sign on the last
 // diagonal's staged entries, together with the Z of the kicks that follow that
-// diagonal pulled back through them (frame12_records' npost; their bits depend
+// diagonal pulled back through them (frame12_walk's npost; their bits depend
 // on the variants only), so the frame is X^x alone at the store, which writes
 // tile index y to y ^ x.  (A launch without any diagonal signs the tile where
 // it applies the global factor.)
@@ -29,7 +29,9 @@
 #pragma once
 #include <stdint.h>
 
-// (no other header: the CPU check compiles this file with a plain host
+#include "dtc_pass_frame.h"  // PauliFrame: the per-kick frame step
+
+// (no HIP header: the CPU check compiles this file with a plain host
 // compiler; dtc_kernels.hip asserts that the two constants are WfArgs')
 #ifdef __HIPCC__
 #define DTC_WF_HD __host__ __device__
@@ -63,10 +65,7 @@ DTC_WF_HD inline int wf_step_bits(uint32_t mask, int act) {
 DTC_WF_HD inline void wf_frame_walk(bool rx, int n_steps, const uint32_t* mask, int dmask,
                                     int act, const int (*var)[kWfFrameBits],
                                     const double (*coef)[kWfFrameBits], WfFrame& o) {
-  auto form_a = [&](int st, int k) { return (var[st][k] >> 1) ^ 1; };
-  auto zbit = [&](int st, int k) {
-    return rx ? (var[st][k] & 1) : ((var[st][k] & 1) ^ form_a(st, k));
-  };
+  auto zbit = [&](int st, int k) { return frame_zbit(rx, var[st][k]); };
   // where Z leaves: the last diagonal applied, or the end of a launch without
   // any (the kernel then signs the tile with its global factor)
   int last = n_steps;
@@ -79,32 +78,25 @@ DTC_WF_HD inline void wf_frame_walk(bool rx, int n_steps, const uint32_t* mask, 
     for (int k = 0; k < kWfFrameBits; ++k)
       if ((bits >> k) & 1) npost ^= zbit(st, k) << k;
   }
-  int x = 0, z = 0, ph = 0;
+  PauliFrame f;
   o.xdiag = 0;
   o.zlast = 0;
   for (int st = 0; st <= n_steps; ++st) {
-    if ((dmask >> st) & 1) o.xdiag |= (uint64_t)x << (kWfFrameBits * st);
+    if ((dmask >> st) & 1) o.xdiag |= (uint64_t)f.x << (kWfFrameBits * st);
     if (st == last) {
-      o.zlast = z ^ npost;
-      z = npost;
+      o.zlast = f.z ^ npost;
+      f.z = npost;
     }
     for (int k = 0; k < kWfFrameBits; ++k) {
       if (st < kWfFrameSteps) o.coef[st][k] = 0.0;
       if (st == n_steps || !((wf_step_bits(mask[st], act) >> k) & 1)) continue;
-      const int fa = form_a(st, k), n2 = zbit(st, k);
-      const double g = fa ? -coef[st][k] : coef[st][k];
-      const int flip = ((rx ? z : (x ^ z)) >> k) & 1;
-      o.coef[st][k] = flip ? -g : g;
-      ph += (rx ? 3 * fa : 2 * fa) + 2 * flip;
-      x ^= fa << k;
-      ph += 2 * (n2 & (x >> k) & 1);
-      z ^= n2 << k;
+      o.coef[st][k] = f.kick(rx, var[st][k], coef[st][k], k);
     }
   }
   for (int st = n_steps + 1; st < kWfFrameSteps; ++st)
     for (int k = 0; k < kWfFrameBits; ++k) o.coef[st][k] = 0.0;
-  o.xend = x;
-  o.ph = ph & 3;
+  o.xend = f.x;
+  o.ph = f.ph & 3;
 }
 
 // ---- tile 2's partial diagonal in layout 1 -----------------------------------
