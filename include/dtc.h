@@ -567,6 +567,60 @@ int dtc_correlation_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise*
  * plain loops, combined with the kernels' own index algebra (csrc/dtc_corr.h). */
 int dtc_correlations_state(const double* state, int32_t L, int32_t basis, double* z, double* zz);
 
+/* Reduced density matrices of site windows of the forward sweep (no reference
+ * counterpart).  A window is k sites s_0 < s_1 < ... < s_{k-1}, 1 <= k <= 4; all
+ * n_win windows of a call share k (sites: [n_win][k]).  With d = 2^k, row index
+ * alpha has bit m equal to the bit of site s_m, and for every trajectory of
+ * dtc_energy and every time t, on the forward state psi after p = t + t_offset
+ * periods,
+ *   rho[alpha][alpha'] = sum_c psi(alpha, c) conj psi(alpha', c),
+ * c running over the other L - k bits: rho = Tr_rest |psi><psi|.  In this
+ * convention <O_{s_1} (x) O_{s_0}> = Tr(rho kron(O_{s_1}, O_{s_0})) (the last
+ * site is the most significant factor), e.g. <Z_{s_0}> = rho[0][0] - rho[1][1]
+ * for k = 1.  rho is not divided by the norm (Tr rho = 1 up to rounding:
+ * depolarizing or noiseless kicks only; the Python wrapper refuses device-like
+ * and bond noise).  The stored matrix is Hermitian bit for bit -- one triangle
+ * is computed, the other is its conjugate -- and the imaginary part of the
+ * diagonal is exactly 0.
+ *
+ * rho is linear in |psi><psi|, so the mean over trajectories estimates the
+ * depolarizing channel's exact reduced state; quantities
+ * that are not linear in rho (entropy, purity, mutual information) must be
+ * taken of that mean, not averaged per trajectory.  The trajectories are
+ * dtc_energy's, trajectory for trajectory (no new draws), reached through the
+ * K-D schedule of dtc_sample and dtc_correlations.
+ *
+ * Row p = 0 is formed on the host from the prepared mask m: rho = |m_A><m_A|,
+ * the single entry 1 at alpha = alpha' = the bits of m at the window's sites.
+ * Rows t < prob->t_first are left 0; want_fwd / want_echo ignored.
+ *
+ * Rows are bit-identical for any batch size, any split of the trajectories and
+ * either batch layout: every sum is a fixed function of the logical index, and
+ * no atomics are used (dtc_rdm.hip; DESIGN.md "Reduced density matrices").
+ *
+ * Each measured state costs one extra read per window (and a small reduce over
+ * the workgroup partials); no basis-change pass.  Launches are counted under
+ * DTC_KERNEL_REDUCE when profiling, the read with 16 B per amplitude.
+ *
+ * rho: [n_inst][n_traj][T][n_win][d][d][2] (re, im).  DTC_EINVAL for null
+ * arguments, n_win < 1, k outside 1..4, k > L, a site outside [0, L), sites of
+ * a window not strictly ascending, L > 32, and T n_win d d > 2^25. */
+int dtc_rdm(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise, uint64_t seed,
+            int64_t traj_offset, int32_t n_traj, const int32_t* sites, int32_t n_win, int32_t k,
+            double* rho);
+/* The same sweep with the per-trajectory matrices summed per instance on the
+ * device: rho_sum [n_inst][T][n_win][d][d][2] (divide by n_traj for the mean
+ * state).  Batch-invariant up to rounding only: an instance's trajectories are
+ * added batch by batch. */
+int dtc_rdm_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise, uint64_t seed,
+                 int64_t traj_offset, int32_t n_traj, const int32_t* sites, int32_t n_win,
+                 int32_t k, double* rho_sum);
+/* host only, the contract's reference: rho [d][d][2] of one window of a host
+ * state of 2^L complex128 amplitudes, by plain sums over c in ascending order
+ * with the kernels' own index algebra (csrc/dtc_rdm.h).  The same checks as
+ * dtc_rdm, without a device. */
+int dtc_rdm_state(const double* state, int32_t L, const int32_t* sites, int32_t k, double* rho);
+
 /* Profiling: when enabled, every kernel launch is bracketed by HIP events on
  * the ctx stream and accumulated per kernel kind. */
 #define DTC_KERNEL_LO_PASS 0   /* fused RZZ+RZ diagonal + low-site kick pass */

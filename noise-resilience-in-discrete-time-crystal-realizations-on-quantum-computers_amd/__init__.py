@@ -18,8 +18,8 @@ from . import _capi  # noqa: E402
 from .kicks import kick_table, POLARIZATIONS, rx, ry  # noqa: E402
 from .disorder import load_disorder, generate_disorder, save_disorder_to_csv  # noqa: E402
 from .engine import DtcEngine, SweepSpec, energy_init_mask, init_mask, N_ANCILLA_NOISY_GATES  # noqa: E402
-from . import circuit, aer, sweep, distributed, sharded, energy, envelopes, control, correlations  # noqa: E402
-from . import cli, energy_cli, control_cli, correlation_cli  # noqa: E402
+from . import circuit, aer, sweep, distributed, sharded, energy, envelopes, control, correlations, entanglement  # noqa: E402
+from . import cli, energy_cli, control_cli, correlation_cli, entanglement_cli  # noqa: E402
 from .circuit import QuantumCircuit, transpile_aer_basis  # noqa: E402
 from .aer import AerSimulator, DtcSimulator, NoiseModel, depolarizing_error  # noqa: E402
 from .device_noise import DeviceNoise, DeviceCalibration  # noqa: E402
@@ -34,5 +34,6 @@ __all__ = [
     "DtcSimulator", "NoiseModel", "depolarizing_error", "run_sweep", "get_instances",
     "get_single_out", "compute_z_expectation", "write_autocorr_csv", "circuit", "aer",
     "sweep", "distributed", "sharded", "energy", "envelopes", "control", "cli", "energy_cli",
-    "control_cli", "correlations", "correlation_cli", "DeviceNoise", "DeviceCalibration", "device_noise",
+    "control_cli", "correlations", "correlation_cli", "entanglement", "entanglement_cli",
+    "DeviceNoise", "DeviceCalibration", "device_noise",
 ]

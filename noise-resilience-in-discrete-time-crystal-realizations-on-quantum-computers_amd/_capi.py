@@ -63,6 +63,9 @@ EXPORTED_SYMBOLS = (
     "dtc_correlations",
     "dtc_correlation_sums",
     "dtc_correlations_state",
+    "dtc_rdm",
+    "dtc_rdm_sums",
+    "dtc_rdm_state",
     "dtc_shard_echo_step",
     "dtc_shard_echo_step_async",
     "dtc_shard_echo_kick_slice",
@@ -80,7 +83,8 @@ KERNEL_NAMES = {
     KERNEL_HI_PASS: "pass_kernel<none>  (kick on sites >= 12)",
     KERNEL_REDUCE: "reduce_kernel, bond_obs_sign_kernel (bond-noise signs of the energy rows), "
                    "sample_weights_kernel / sample_pick_kernel (measurement sampling), "
-                   "corr_chunk_kernel / corr_reduce_kernel (all-pair correlators)",
+                   "corr_chunk_kernel / corr_reduce_kernel (all-pair correlators), "
+                   "rdm_gram_kernel / rdm_reduce_kernel (reduced density matrices)",
     KERNEL_INIT: "bond_diag_kernel (bond-noise diagonal tables per state, dtc_autocorr_bond)",
     KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split / the last dtc_xend_pass of an energy "
                        "echo chain / dtc_kick_sites_final, the end of a sharded echo chain "
@@ -334,6 +338,14 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         ]
         lib.dtc_correlation_sums.argtypes = lib.dtc_correlations.argtypes
         lib.dtc_correlations_state.argtypes = [_dp, ctypes.c_int32, ctypes.c_int32, _dp, _dp]
+        lib.dtc_rdm.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), ctypes.c_uint64, ctypes.c_int64,
+            ctypes.c_int32, P(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, _dp,
+        ]
+        lib.dtc_rdm_sums.argtypes = lib.dtc_rdm.argtypes
+        lib.dtc_rdm_state.argtypes = [
+            _dp, ctypes.c_int32, P(ctypes.c_int32), ctypes.c_int32, _dp,
+        ]
         for name in EXPORTED_SYMBOLS:
             if name not in ("dtc_last_error", "dtc_abi_version"):
                 getattr(lib, name).restype = ctypes.c_int

@@ -30,6 +30,7 @@
 
 #include "../../include/dtc.h"
 #include "dtc_corr.h"
+#include "dtc_rdm.h"
 #include "dtc_kernels.h"
 #include "dtc_rng.h"
 #include "dtc_schedule.h"
@@ -98,6 +99,9 @@ struct dtc_ctx {
   // all-pair correlators (dtc_correlations): the chunk partials of the state
   // being measured, [batch][n_tiles][79]
   DevBuf corr_part;
+  // reduced density matrices (dtc_rdm): the workgroup partials of the window
+  // being measured, [batch][rdm::n_workgroups(L_eff)][512]
+  DevBuf rdm_part;
   std::vector<dtc::PassKick> pk_host;   // staged pass list (alive until the stream syncs)
   // forward prefix (dtc_prefix_build): every trajectory's state after
   // prefix_periods periods, and what it was built from
@@ -994,6 +998,7 @@ int dtc_close(dtc_ctx* ctx) {
   release(ctx->sample_w);
   release(ctx->sample_bits);
   release(ctx->corr_part);
+  release(ctx->rdm_part);
   for (auto& e : ctx->shard_cache) release(e.diag);
   for (auto& e : ctx->shard_maps) release(e.diag);
   release(ctx->shard_kick);
@@ -1018,6 +1023,7 @@ int dtc_release_buffers(dtc_ctx* ctx) {
   release(ctx->sample_w);
   release(ctx->sample_bits);
   release(ctx->corr_part);
+  release(ctx->rdm_part);
   return DTC_OK;
 }
 
@@ -2389,6 +2395,193 @@ int dtc_correlations_state(const double* state, int32_t L, int32_t basis, double
     for (size_t c = 0; c < n_chunks; ++c) acc += cr::term(&part[c * cr::kPartial], src, c);
     (o < L ? z[o] : zz[o - L]) = acc;
   }
+  return DTC_OK;
+}
+
+namespace {
+
+// The two launches of one window on a batch's states F: the matrices go to
+// out[b * out_stride ..].  Booked under DTC_KERNEL_REDUCE: the Gram kernel with
+// the batch's 16 B per amplitude, the reduce with the partials and its rows.
+int launch_rdm(dtc_ctx* ctx, const RunCfg& rc, int batch, const double2* st,
+               const dtc::rdm::Geom& g, double* out, int64_t out_stride) {
+  dtc::RdmArgs A{};
+  A.state = st;
+  A.partial = (double*)ctx->rdm_part.p;
+  A.out = out;
+  A.out_stride = out_stride;
+  A.L_eff = rc.pl.L_eff;
+  A.octet_bits = rc.octet_bits;
+  A.batch = batch;
+  A.g = g;
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE, 16.0 * (double)rc.pl.len * batch,
+            dtc::launch_rdm_gram(A, ctx->stream));
+  DTC_TIMED(ctx, DTC_KERNEL_REDUCE,
+            8.0 * batch *
+                ((double)dtc::rdm::n_workgroups(rc.pl.L_eff) * dtc::rdm::kPartial +
+                 (double)((size_t)2 << (2 * g.k))),
+            dtc::launch_rdm_reduce(A, ctx->stream));
+  return DTC_OK;
+}
+
+int check_windows(const int32_t* sites, int32_t n_win, int32_t k, int L) {
+  if (!sites) return fail(DTC_EINVAL, "null sites");
+  if (n_win < 1) return fail(DTC_EINVAL, "n_win must be >= 1");
+  if (k < 1 || k > dtc::rdm::kMaxK) return fail(DTC_EINVAL, "window size k must be in [1, 4]");
+  for (int32_t w = 0; w < n_win; ++w)
+    if (const char* err = dtc::rdm::check_window(sites + (size_t)w * k, k, L))
+      return fail(DTC_EINVAL, err);
+  return DTC_OK;
+}
+
+// sums: rho is the per-instance sum over the trajectories ([n_inst][T][.],
+// dtc_rdm_sums) instead of per-trajectory rows
+int rdm_impl(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+             int64_t traj_offset, int32_t n_traj, const int32_t* sites, int32_t n_win, int32_t k,
+             double* rho, bool sums) {
+  if (!ctx || !rho) return fail(DTC_EINVAL, "null ctx/output");
+  DTC_TRY(check_problem(pr, nz));
+  DTC_TRY(check_windows(sites, n_win, k, pr->L));
+  RunCfg rc;
+  DTC_TRY(init_run_cfg(ctx, pr, nz, nullptr, nullptr, seed, traj_offset, n_traj, false, rc));
+  const Plan& pl = rc.pl;
+  const int T = pr->T;
+  const int P = T - 1 + pr->t_offset;
+  const int64_t S = (int64_t)pr->n_inst * n_traj;
+  const size_t mat = (size_t)2 << (2 * k);         // doubles per matrix: d d 2
+  const size_t row = (size_t)T * n_win * mat;      // doubles per state
+  const size_t n_rows = (size_t)(sums ? pr->n_inst : S);
+  if ((double)T * n_win * (double)mat > (double)(1u << 26))
+    return fail(DTC_EINVAL, "T n_win d d exceeds 2^25 matrix entries per state");
+  std::fill(rho, rho + n_rows * row, 0.0);
+
+  // Row p = 0: the prepared basis state |m>, rho = |m_A><m_A|.
+  if (pr->t_offset == 0 && pr->t_first == 0) {
+    for (int64_t s = 0; s < S; ++s) {
+      const uint64_t m = init_state_mask(rc, (uint64_t)(traj_offset + s % n_traj));
+      double* r = rho + (size_t)(sums ? s / n_traj : s) * row;
+      for (int32_t w = 0; w < n_win; ++w) {
+        size_t al = 0;
+        for (int i = 0; i < k; ++i) al |= (size_t)((m >> sites[(size_t)w * k + i]) & 1ull) << i;
+        r[(size_t)w * mat + 2 * ((al << k) + al)] += 1.0;
+      }
+    }
+  }
+  if (P == 0) return DTC_OK;
+  DTC_TRY(upload_tables(ctx, pr, pl));
+
+  std::vector<dtc::rdm::Geom> geo((size_t)n_win);
+  for (int32_t w = 0; w < n_win; ++w)
+    geo[w] = dtc::rdm::geometry(sites + (size_t)w * k, k, pl.L_eff);
+
+  // (the rows of a batch: at most 512 MiB)
+  const double per_state = (double)pl.len * 16.0;
+  Batch bt;
+  DTC_TRY(plan_batch(ctx, rc, per_state, ctx->F.n, false,
+                     std::max<int64_t>(1, (int64_t)((size_t)(1u << 26) / row)), false, -1, bt));
+  const int64_t B = bt.B;
+  DTC_TRY(ensure(ctx->rdm_part, (size_t)B * (size_t)dtc::rdm::n_workgroups(pl.L_eff) *
+                                    dtc::rdm::kPartial * sizeof(double)));
+  DTC_TRY(ensure(ctx->vals_f, (size_t)B * row * sizeof(double)));
+  // per-instance sums: at most (B - 1) / n_traj + 2 instances per batch
+  const int64_t max_inst_b = std::min<int64_t>(pr->n_inst, (B - 1) / n_traj + 2);
+  const size_t n_host = (size_t)(sums ? max_inst_b : B) * row;
+  if (sums) DTC_TRY(ensure(ctx->vals_e, n_host * sizeof(double)));
+  DTC_TRY(ensure_host(ctx->host_f, n_host));
+  double* const hv = ctx->host_f.p;
+  std::vector<int64_t> masks(B);
+
+  // the schedule (build_sample_schedule, dtc_schedule.h) is the same for every
+  // batch; the state a pass leaves at a time is read once per window
+  double2* const F = (double2*)ctx->F.p;
+  double* const rv = (double*)ctx->vals_f.p;
+  std::vector<Launch> sched = build_sample_schedule(rc, F);
+  // rows the device does not write (t < t_first, and p = 0, formed above)
+  const int t0 = std::max(pr->t_first, pr->t_offset == 0 ? 1 : 0);
+
+  for (int64_t bs = 0; bs < S; bs += B) {
+    const int nb = (int)std::min<int64_t>(B, S - bs);
+    DTC_TRY(batch_masks(ctx, rc, bs, nb, masks));
+    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, bt.octet));
+    DTC_HIP(hipMemsetAsync(rv, 0, (size_t)B * row * sizeof(double), ctx->stream));
+    const AfterLaunch measure = [&](const Launch& l) -> int {
+      for (int32_t w = 0; w < n_win; ++w)
+        DTC_TRY(launch_rdm(ctx, rc, nb, F, geo[w],
+                           rv + ((size_t)l.t_state * n_win + w) * mat, (int64_t)row));
+      return DTC_OK;
+    };
+    DTC_TRY(run_launches(ctx, rc, bs, nb, sched, measure));
+    // the batch's rows, or their sums per instance (traj_sum_kernel)
+    const int64_t i0 = bs / n_traj, n_ib = (bs + nb - 1) / n_traj - i0 + 1;
+    const size_t n_get = (size_t)(sums ? n_ib : nb) * row;
+    const double* src = rv;
+    if (sums) {
+      double* dsum = (double*)ctx->vals_e.p;
+      DTC_HIP(dtc::launch_traj_sum(src, nb, (int)row, bs, n_traj, dsum, ctx->stream));
+      src = dsum;
+    }
+    DTC_HIP(hipMemcpyAsync(hv, src, n_get * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    DTC_HIP(hipStreamSynchronize(ctx->stream));
+    DTC_TRY(settle_pending(ctx));
+    const int64_t n_r = sums ? n_ib : nb, r0 = sums ? i0 : bs;
+    const size_t per_t = (size_t)n_win * mat;
+    for (int64_t r = 0; r < n_r; ++r) {
+      // (sums: an instance's trajectories may span batches)
+      const double* v = hv + (size_t)r * row;
+      double* o = rho + (size_t)(r0 + r) * row;
+      for (size_t i = (size_t)t0 * per_t; i < row; ++i) o[i] += v[i];
+    }
+  }
+  return DTC_OK;
+}
+
+}  // namespace
+
+int dtc_rdm(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+            int64_t traj_offset, int32_t n_traj, const int32_t* sites, int32_t n_win, int32_t k,
+            double* rho) {
+  return rdm_impl(ctx, pr, nz, seed, traj_offset, n_traj, sites, n_win, k, rho, false);
+}
+
+int dtc_rdm_sums(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+                 int64_t traj_offset, int32_t n_traj, const int32_t* sites, int32_t n_win,
+                 int32_t k, double* rho_sum) {
+  return rdm_impl(ctx, pr, nz, seed, traj_offset, n_traj, sites, n_win, k, rho_sum, true);
+}
+
+int dtc_rdm_state(const double* state, int32_t L, const int32_t* sites, int32_t k, double* rho) {
+  namespace rd = dtc::rdm;
+  if (!state || !sites || !rho) return fail(DTC_EINVAL, "null argument");
+  if (L < 1 || L > 32) return fail(DTC_EINVAL, "L must be in [1, 32]");
+  if (const char* err = rd::check_window(sites, k, L)) return fail(DTC_EINVAL, err);
+  const int d = 1 << k;
+  int pos[rd::kMaxK];
+  uint64_t off[rd::kRows];
+  for (int m = 0; m < k; ++m) pos[m] = sites[m];
+  for (int a = 0; a < d; ++a) off[a] = rd::row_offset(a, pos, k);
+  // the lower triangle by plain sums over the column index in ascending order
+  std::vector<double> re((size_t)d * d, 0.0), im((size_t)d * d, 0.0);
+  const uint64_t n_cols = (uint64_t)1 << (L - k);
+  for (uint64_t c = 0; c < n_cols; ++c) {
+    const uint64_t x0 = rd::spread_cols(c, pos, k);
+    for (int a = 0; a < d; ++a) {
+      const double ar = state[2 * (x0 | off[a])], ai = state[2 * (x0 | off[a]) + 1];
+      for (int a2 = 0; a2 <= a; ++a2) {
+        const double br = state[2 * (x0 | off[a2])], bi = state[2 * (x0 | off[a2]) + 1];
+        re[(size_t)a * d + a2] += ar * br + ai * bi;
+        im[(size_t)a * d + a2] += ai * br - ar * bi;
+      }
+    }
+  }
+  for (int a = 0; a < d; ++a)
+    for (int a2 = 0; a2 <= a; ++a2) {
+      const double gr = re[(size_t)a * d + a2], gi = a == a2 ? 0.0 : im[(size_t)a * d + a2];
+      rho[2 * ((size_t)a * d + a2)] = gr;
+      rho[2 * ((size_t)a * d + a2) + 1] = gi;
+      if (a == a2) continue;
+      rho[2 * ((size_t)a2 * d + a)] = gr;
+      rho[2 * ((size_t)a2 * d + a) + 1] = -gi;
+    }
   return DTC_OK;
 }
 

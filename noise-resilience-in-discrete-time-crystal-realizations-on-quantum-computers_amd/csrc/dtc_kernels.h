@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "dtc_pass_frame.h"
+#include "dtc_rdm.h"
 
 namespace dtc {
 
@@ -521,5 +522,25 @@ struct CorrArgs {
 };
 hipError_t launch_corr_chunk(const CorrArgs& a, hipStream_t stream);
 hipError_t launch_corr_reduce(const CorrArgs& a, hipStream_t stream);
+
+// Reduced density matrices of site windows (dtc_rdm.hip, dtc_rdm.h;
+// include/dtc.h dtc_rdm): rho[alpha][alpha'] of one window of every state of a
+// batch.  Two launches per batch and window:
+//  * gram: one read-only sweep of the batch; each workgroup's 16 x 16 Gram sums
+//    over its tiles (FP64 MFMA) into partial[b][workgroup][512] (Re G | X);
+//  * reduce: per state the partials added in an order that depends on the
+//    workgroup index alone, the block trace over the pad bits, Im G = X - X^T,
+//    and the Hermitian d x d matrix into out[b * out_stride + (a d + a') 2 + re/im].
+struct RdmArgs {
+  const double2* state;    // the batch, in the layout of octet_bits
+  double* partial;         // [batch][rdm::n_workgroups(L_eff)][512]
+  double* out;             // [batch] matrices [d][d][2], out_stride doubles apart
+  int64_t out_stride;
+  int L_eff, octet_bits;
+  int batch;
+  rdm::Geom g;             // rdm::geometry(sites, k, L_eff)
+};
+hipError_t launch_rdm_gram(const RdmArgs& a, hipStream_t stream);
+hipError_t launch_rdm_reduce(const RdmArgs& a, hipStream_t stream);
 
 }  // namespace dtc

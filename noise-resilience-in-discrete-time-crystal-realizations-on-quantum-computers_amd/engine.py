@@ -223,6 +223,49 @@ def correlations_state(psi, L: int, basis: int):
     return z, zz
 
 
+def refuse_rdm(spec: SweepSpec, what: str) -> None:
+    """The reduced density matrices run depolarizing or noiseless kicks only."""
+    if getattr(spec, "device", None) is not None:
+        raise NotImplementedError(
+            f"{what} does not support device-like noise (SweepSpec.device): the density-matrix "
+            "sweep has no Kraus kick kinds (rho stays linear there; not built)")
+    if getattr(spec, "has_bond_noise", False):
+        raise NotImplementedError(
+            f"{what} does not support bond noise (SweepSpec.bond_noise): there is no density-"
+            "matrix entry point taking its per-state diagonal tables")
+
+
+def window_array(windows) -> np.ndarray:
+    """``windows`` (one window of sites, or a list of windows of one size) as a
+    contiguous int32 [n_win][k] array.  Validity is the library's to check."""
+    w = np.asarray(windows, dtype=np.int64)
+    if w.ndim == 1:
+        w = w[None, :]
+    if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] < 1:
+        raise ValueError("windows must be [n_win][k] site lists of one size k")
+    return np.ascontiguousarray(w.astype(np.int32))
+
+
+def rdm_state(psi, L: int, sites) -> np.ndarray:
+    """Host only (dtc_rdm_state), the density-matrix contract's reference: the
+    complex128 [d][d] matrix ``rho[a][a'] = sum_c psi(a, c) conj psi(a', c)`` of
+    the window ``sites`` (ascending, at most 4) of the state ``psi`` (2^L
+    amplitudes, site i = bit i); bit m of ``a`` is the bit of ``sites[m]``."""
+    lib = _capi.load_library()
+    buf = np.ascontiguousarray(np.asarray(psi, dtype=np.complex128).reshape(-1))
+    if buf.size != 1 << L:
+        raise ValueError(f"psi must hold 2^L = {1 << L} amplitudes")
+    s = np.ascontiguousarray(np.asarray(sites, dtype=np.int32).reshape(-1))
+    k = int(s.size)
+    d = 1 << k if 1 <= k <= 4 else 1  # (a bad k is the library's to refuse)
+    rho = np.zeros((d, d), dtype=np.complex128)
+    _capi.check(lib.dtc_rdm_state(
+        _capi.as_dptr(buf.view(np.float64)), ctypes.c_int32(L),
+        s.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.c_int32(k),
+        _capi.as_dptr(rho.view(np.float64))))
+    return rho
+
+
 def bond_struct(p_bond: np.ndarray) -> "_capi.DtcBondNoise":
     b = _capi.DtcBondNoise()
     b.p_bond = _capi.as_dptr(p_bond)
@@ -638,6 +681,42 @@ class DtcEngine:
         for the means."""
         return self._correlations("dtc_correlation_sums", "correlation_sums", spec,
                                   (spec.n_inst,), n_traj, bases, seed, traj_offset, batch, t_first)
+
+    def _rdm(self, fn: str, what: str, spec: SweepSpec, lead: tuple, n_traj: int, windows,
+             seed: int, traj_offset: int, batch: int, t_first: int) -> np.ndarray:
+        refuse_rdm(spec, what)
+        win = window_array(windows)
+        n_win, k = win.shape
+        if not 1 <= k <= 4:
+            raise ValueError(f"window size must be in [1, 4], got {k}")
+        d = 1 << k
+        rho = np.zeros(lead + (spec.T, n_win, d, d), dtype=np.complex128)
+        pr = self._problem(spec, True, False, batch, t_first)
+        _capi.check(getattr(self._lib, fn)(
+            self._ctx, ctypes.byref(pr), ctypes.byref(self._noise(spec)), ctypes.c_uint64(seed),
+            ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj),
+            win.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.c_int32(n_win),
+            ctypes.c_int32(k), _capi.as_dptr(rho.view(np.float64))))
+        return rho
+
+    def rdm(self, spec: SweepSpec, n_traj: int, windows, seed: int = 0x5EED0001,
+            batch: int = 0, traj_offset: int = 0, t_first: int = 0) -> np.ndarray:
+        """Reduced density matrices of site windows of the forward sweep
+        (dtc_rdm): complex128 [n_inst][n_traj][T][n_win][d][d], d = 2^k, for every
+        trajectory of ``energy`` and every time t.  ``windows`` is one window or a
+        list of windows of one size k <= 4, each strictly ascending; bit m of a
+        row index is the bit of the window's m-th site.  Rows before ``t_first``
+        stay 0.  Depolarizing or noiseless kicks only."""
+        return self._rdm("dtc_rdm", "rdm", spec, (spec.n_inst, int(n_traj)), n_traj, windows,
+                         seed, traj_offset, batch, t_first)
+
+    def rdm_sums(self, spec: SweepSpec, n_traj: int, windows, seed: int = 0x5EED0001,
+                 batch: int = 0, traj_offset: int = 0, t_first: int = 0) -> np.ndarray:
+        """``rdm`` summed over each instance's ``n_traj`` trajectories on the
+        device (dtc_rdm_sums): [n_inst][T][n_win][d][d].  Divide by ``n_traj``
+        for the noise-averaged state."""
+        return self._rdm("dtc_rdm_sums", "rdm_sums", spec, (spec.n_inst,), n_traj, windows,
+                         seed, traj_offset, batch, t_first)
 
     # -- sharded state (dtc_shard_*; driver: sharded.py) ----------------
     def shard_set_basis(self, spec: SweepSpec, shard, state_ptr: int, seed: int = 0x5EED0001,
