@@ -28,8 +28,8 @@ OBJDIR  := build/obj
 LIB     := $(PKG)/lib/libdtc_hip.so
 ORACLE  := oracle/liboracle.so
 ORACLE3 := oracle/liboracle_v3.so
-SRCS    := $(PKG)/csrc/dtc_kernels.hip $(PKG)/csrc/dtc_lightcone.hip $(PKG)/csrc/dtc_tile13.hip $(PKG)/csrc/dtc_bond.hip $(PKG)/csrc/dtc_wavefront.hip $(PKG)/csrc/dtc_sample.hip $(PKG)/csrc/dtc_corr.hip $(PKG)/csrc/dtc_rdm.hip $(PKG)/csrc/dtc_engine.cpp
-HDRS    := $(PKG)/csrc/dtc_kernels.h $(PKG)/csrc/dtc_device.h $(PKG)/csrc/dtc_rng.h $(PKG)/csrc/dtc_wavefront.h $(PKG)/csrc/dtc_wf_frame.h $(PKG)/csrc/dtc_pass_frame.h $(PKG)/csrc/dtc_corr.h $(PKG)/csrc/dtc_rdm.h include/dtc.h
+SRCS    := $(PKG)/csrc/dtc_kernels.hip $(PKG)/csrc/dtc_lightcone.hip $(PKG)/csrc/dtc_tile13.hip $(PKG)/csrc/dtc_bond.hip $(PKG)/csrc/dtc_wavefront.hip $(PKG)/csrc/dtc_sample.hip $(PKG)/csrc/dtc_corr.hip $(PKG)/csrc/dtc_rdm.hip $(PKG)/csrc/dtc_rdm_block.hip $(PKG)/csrc/dtc_engine.cpp
+HDRS    := $(PKG)/csrc/dtc_kernels.h $(PKG)/csrc/dtc_device.h $(PKG)/csrc/dtc_rng.h $(PKG)/csrc/dtc_wavefront.h $(PKG)/csrc/dtc_wf_frame.h $(PKG)/csrc/dtc_pass_frame.h $(PKG)/csrc/dtc_corr.h $(PKG)/csrc/dtc_rdm.h $(PKG)/csrc/dtc_rdm_block.h include/dtc.h
 
 all: $(LIB) $(ORACLE) $(ORACLE3)
 
@@ -70,12 +70,16 @@ $(OBJDIR)/dtc_rdm.o: $(PKG)/csrc/dtc_rdm.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
 
+$(OBJDIR)/dtc_rdm_block.o: $(PKG)/csrc/dtc_rdm_block.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
+
 # (the schedule header is host code of the engine alone: the kernels do not see it)
 $(OBJDIR)/dtc_engine.o: $(PKG)/csrc/dtc_engine.cpp $(PKG)/csrc/dtc_schedule.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPCFLAGS) -c $< -o $@
 
-$(LIB): $(OBJDIR)/dtc_kernels.o $(OBJDIR)/dtc_lightcone.o $(OBJDIR)/dtc_tile13.o $(OBJDIR)/dtc_bond.o $(OBJDIR)/dtc_wavefront.o $(OBJDIR)/dtc_sample.o $(OBJDIR)/dtc_corr.o $(OBJDIR)/dtc_rdm.o $(OBJDIR)/dtc_engine.o
+$(LIB): $(OBJDIR)/dtc_kernels.o $(OBJDIR)/dtc_lightcone.o $(OBJDIR)/dtc_tile13.o $(OBJDIR)/dtc_bond.o $(OBJDIR)/dtc_wavefront.o $(OBJDIR)/dtc_sample.o $(OBJDIR)/dtc_corr.o $(OBJDIR)/dtc_rdm.o $(OBJDIR)/dtc_rdm_block.o $(OBJDIR)/dtc_engine.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) --offload-arch=$(ARCH) -shared $^ -o $@
 

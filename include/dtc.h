@@ -621,6 +621,52 @@ int dtc_rdm_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise, 
  * dtc_rdm, without a device. */
 int dtc_rdm_state(const double* state, int32_t L, const int32_t* sites, int32_t k, double* rho);
 
+/* Reduced density matrices of blocks of contiguous sites of the forward sweep
+ * (no reference counterpart): the half-chain entanglement.  A block is the k
+ * sites a, a+1, ..., a+k-1, given as its start a; all n_blk blocks of a call
+ * share k, 5 <= k <= 10 (k <= 4: dtc_rdm).  Index convention of dtc_rdm: with
+ * d = 2^k, bit m of a row index is the bit of site a + m, and
+ *   rho[alpha][alpha'] = sum_c psi(alpha, c) conj psi(alpha', c)
+ * on the forward state psi after p = t + t_offset periods.  The sweep, the
+ * trajectories and the draws are dtc_rdm's (the K-D schedule of dtc_sample; no
+ * new draws).  Depolarizing or noiseless kicks only; the Python wrapper refuses
+ * device-like and bond noise.
+ *
+ * rho_sum [n_inst][T][n_blk][d][d][2] (nullable): the sum over an instance's
+ * trajectories of the per-state rho; nothing is divided by the norm or by
+ * n_traj.  Hermitian bit for bit -- one triangle is computed, the other is its
+ * conjugate -- with the diagonal's imaginary part exactly 0.  Batch-invariant up
+ * to rounding only, like dtc_rdm_sums.  Linear in |psi><psi|: the trajectory
+ * mean is the depolarizing channel's exact reduced state.
+ *
+ * purity [n_inst][n_traj][T][n_blk] (nullable; not both null):
+ * sum_{alpha alpha'} |rho[alpha][alpha']|^2 of that trajectory's own (pure)
+ * state: -ln of it is the trajectory-resolved second Renyi entanglement
+ * entropy.  Summed in an order that is a function of the logical index alone:
+ * rows are bit-identical for any batch size, any split of the trajectories and
+ * either batch layout.  No atomics anywhere.
+ *
+ * Row p = 0 is formed on the host from the prepared mask m: rho = |m_A><m_A|,
+ * purity 1.  Rows t < prob->t_first are left 0; want_fwd / want_echo ignored.
+ *
+ * Cost per measured state and block: about 2^(L+k+2) FP64 flops (the lower
+ * triangle, FP64 MFMA) against the state's 16 B per amplitude; compute-bound
+ * beyond k = 5..6 (DESIGN.md "Block density matrices").  Launches are counted
+ * under DTC_KERNEL_REDUCE when profiling.
+ *
+ * DTC_EINVAL, before any device call, for null arguments, n_blk < 1, k outside
+ * 5..10, 2 k > L, start < 0, start + k > L, L > 32 and T n_blk d d > 2^25. */
+int dtc_rdm_block_sums(dtc_ctx* ctx, const dtc_problem* prob, const dtc_noise* noise,
+                       uint64_t seed, int64_t traj_offset, int32_t n_traj, const int32_t* starts,
+                       int32_t n_blk, int32_t k, double* rho_sum, double* purity);
+/* host only, the contract's reference: rho [d][d][2] (nullable) and purity [1]
+ * of one block of a host state of 2^L complex128 amplitudes, by plain loops over
+ * the column index in ascending order with the kernels' own index algebra
+ * (csrc/dtc_rdm_block.h).  The same block checks, without a device.  Agrees with
+ * the device to rounding, not to bits. */
+int dtc_rdm_block_state(const double* state, int32_t L, int32_t start, int32_t k, double* rho,
+                        double* purity);
+
 /* Profiling: when enabled, every kernel launch is bracketed by HIP events on
  * the ctx stream and accumulated per kernel kind. */
 #define DTC_KERNEL_LO_PASS 0   /* fused RZZ+RZ diagonal + low-site kick pass */

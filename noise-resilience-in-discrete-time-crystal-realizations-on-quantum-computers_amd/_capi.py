@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = (
     "dtc_rdm",
     "dtc_rdm_sums",
     "dtc_rdm_state",
+    "dtc_rdm_block_sums",
+    "dtc_rdm_block_state",
     "dtc_shard_echo_step",
     "dtc_shard_echo_step_async",
     "dtc_shard_echo_kick_slice",
@@ -84,7 +86,9 @@ KERNEL_NAMES = {
     KERNEL_REDUCE: "reduce_kernel, bond_obs_sign_kernel (bond-noise signs of the energy rows), "
                    "sample_weights_kernel / sample_pick_kernel (measurement sampling), "
                    "corr_chunk_kernel / corr_reduce_kernel (all-pair correlators), "
-                   "rdm_gram_kernel / rdm_reduce_kernel (reduced density matrices)",
+                   "rdm_gram_kernel / rdm_reduce_kernel (reduced density matrices), "
+                   "rdm_block_gram_kernel / rdm_block_finish_kernel / rdm_block_purity_kernel "
+                   "(block density matrices, with their traj_sum_kernel)",
     KERNEL_INIT: "bond_diag_kernel (bond-noise diagonal tables per state, dtc_autocorr_bond)",
     KERNEL_FINAL_PASS: "dtc_*_final / dtc_lc_final_split / the last dtc_xend_pass of an energy "
                        "echo chain / dtc_kick_sites_final, the end of a sharded echo chain "
@@ -345,6 +349,13 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         lib.dtc_rdm_sums.argtypes = lib.dtc_rdm.argtypes
         lib.dtc_rdm_state.argtypes = [
             _dp, ctypes.c_int32, P(ctypes.c_int32), ctypes.c_int32, _dp,
+        ]
+        lib.dtc_rdm_block_sums.argtypes = [
+            ctypes.c_void_p, P(DtcProblem), P(DtcNoise), ctypes.c_uint64, ctypes.c_int64,
+            ctypes.c_int32, P(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, _dp, _dp,
+        ]
+        lib.dtc_rdm_block_state.argtypes = [
+            _dp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _dp, _dp,
         ]
         for name in EXPORTED_SYMBOLS:
             if name not in ("dtc_last_error", "dtc_abi_version"):

@@ -31,6 +31,7 @@
 #include "../../include/dtc.h"
 #include "dtc_corr.h"
 #include "dtc_rdm.h"
+#include "dtc_rdm_block.h"
 #include "dtc_kernels.h"
 #include "dtc_rng.h"
 #include "dtc_schedule.h"
@@ -102,6 +103,11 @@ struct dtc_ctx {
   // reduced density matrices (dtc_rdm): the workgroup partials of the window
   // being measured, [batch][rdm::n_workgroups(L_eff)][512]
   DevBuf rdm_part;
+  // block density matrices (dtc_rdm_block_sums): the split partials
+  // [batch][n_split][de][de][2], the per-state matrices of the time being
+  // measured [batch][d][d][2], and the instance sums of a batch
+  // [T][n_blk][instances][d][d][2]
+  DevBuf rdmb_part, rdmb_work, rdmb_sum;
   std::vector<dtc::PassKick> pk_host;   // staged pass list (alive until the stream syncs)
   // forward prefix (dtc_prefix_build): every trajectory's state after
   // prefix_periods periods, and what it was built from
@@ -999,6 +1005,9 @@ int dtc_close(dtc_ctx* ctx) {
   release(ctx->sample_bits);
   release(ctx->corr_part);
   release(ctx->rdm_part);
+  release(ctx->rdmb_part);
+  release(ctx->rdmb_work);
+  release(ctx->rdmb_sum);
   for (auto& e : ctx->shard_cache) release(e.diag);
   for (auto& e : ctx->shard_maps) release(e.diag);
   release(ctx->shard_kick);
@@ -1024,6 +1033,9 @@ int dtc_release_buffers(dtc_ctx* ctx) {
   release(ctx->sample_bits);
   release(ctx->corr_part);
   release(ctx->rdm_part);
+  release(ctx->rdmb_part);
+  release(ctx->rdmb_work);
+  release(ctx->rdmb_sum);
   return DTC_OK;
 }
 
@@ -2582,6 +2594,201 @@ int dtc_rdm_state(const double* state, int32_t L, const int32_t* sites, int32_t 
       rho[2 * ((size_t)a2 * d + a)] = gr;
       rho[2 * ((size_t)a2 * d + a) + 1] = -gi;
     }
+  return DTC_OK;
+}
+
+namespace {
+
+int check_blocks(const int32_t* starts, int32_t n_blk, int32_t k, int L) {
+  if (!starts) return fail(DTC_EINVAL, "null starts");
+  if (n_blk < 1) return fail(DTC_EINVAL, "n_blk must be >= 1");
+  for (int32_t w = 0; w < n_blk; ++w)
+    if (const char* err = dtc::rdmb::check_block(starts[w], k, L)) return fail(DTC_EINVAL, err);
+  return DTC_OK;
+}
+
+}  // namespace
+
+int dtc_rdm_block_sums(dtc_ctx* ctx, const dtc_problem* pr, const dtc_noise* nz, uint64_t seed,
+                       int64_t traj_offset, int32_t n_traj, const int32_t* starts, int32_t n_blk,
+                       int32_t k, double* rho_sum, double* purity) {
+  namespace rb = dtc::rdmb;
+  if (!ctx || (!rho_sum && !purity)) return fail(DTC_EINVAL, "null ctx/outputs");
+  DTC_TRY(check_problem(pr, nz));
+  DTC_TRY(check_blocks(starts, n_blk, k, pr->L));
+  const int T = pr->T;
+  const size_t mat = (size_t)2 << (2 * k);         // doubles per matrix: d d 2
+  if ((double)T * n_blk * (double)mat > (double)(1u << 26))
+    return fail(DTC_EINVAL, "T n_blk d d exceeds 2^25 matrix entries per instance");
+  RunCfg rc;
+  DTC_TRY(init_run_cfg(ctx, pr, nz, nullptr, nullptr, seed, traj_offset, n_traj, false, rc));
+  const Plan& pl = rc.pl;
+  const int P = T - 1 + pr->t_offset;
+  const int64_t S = (int64_t)pr->n_inst * n_traj;
+  const size_t row = (size_t)T * n_blk * mat;      // doubles per instance
+  const size_t prow = (size_t)T * n_blk;           // purities per state
+  if (rho_sum) std::fill(rho_sum, rho_sum + (size_t)pr->n_inst * row, 0.0);
+  if (purity) std::fill(purity, purity + (size_t)S * prow, 0.0);
+
+  // Row p = 0: the prepared basis state |m>, rho = |m_A><m_A|, purity 1.
+  if (pr->t_offset == 0 && pr->t_first == 0) {
+    for (int64_t s = 0; s < S; ++s) {
+      const uint64_t m = init_state_mask(rc, (uint64_t)(traj_offset + s % n_traj));
+      for (int32_t w = 0; w < n_blk; ++w) {
+        const size_t al = (size_t)((m >> starts[w]) & (((uint64_t)1 << k) - 1));
+        if (rho_sum)
+          rho_sum[(size_t)(s / n_traj) * row + (size_t)w * mat + 2 * ((al << k) + al)] += 1.0;
+        if (purity) purity[(size_t)s * prow + w] = 1.0;
+      }
+    }
+  }
+  if (P == 0) return DTC_OK;
+  DTC_TRY(upload_tables(ctx, pr, pl));
+
+  std::vector<rb::Geom> geo((size_t)n_blk);
+  size_t part_doubles = 0;   // per state
+  for (int32_t w = 0; w < n_blk; ++w) {
+    geo[w] = rb::geometry(starts[w], k, pl.L_eff);
+    if (geo[w].n_split > 1 || geo[w].n_pad > 1)
+      part_doubles =
+          std::max(part_doubles, (size_t)geo[w].n_split * ((size_t)2 << (2 * geo[w].ke)));
+  }
+
+  // A batch holds at most max_inst instances' sums ([T][n_blk][.][d][d][2], at
+  // most 2^28 doubles), which caps its states; the states, their matrices and
+  // partials and their share of the sums count against the memory budget.
+  const int64_t max_inst_cap = std::max<int64_t>(4, (int64_t)(((size_t)1 << 28) / row));
+  const int64_t cap_B = rho_sum ? (max_inst_cap - 2) * (int64_t)n_traj + 1 : 0;
+  const double per_state = (double)pl.len * 16.0 + 8.0 * (double)(mat + part_doubles) +
+                           (rho_sum ? 8.0 * (double)row / n_traj : 0.0);
+  Batch bt;
+  DTC_TRY(plan_batch(ctx, rc, per_state, ctx->F.n, false, cap_B, false, -1, bt));
+  const int64_t B = bt.B;
+  const int64_t max_inst_b = std::min<int64_t>(pr->n_inst, (B - 1) / n_traj + 2);
+  DTC_TRY(ensure(ctx->rdmb_work, (size_t)B * mat * sizeof(double)));
+  if (part_doubles) DTC_TRY(ensure(ctx->rdmb_part, (size_t)B * part_doubles * sizeof(double)));
+  DTC_TRY(ensure(ctx->vals_f, (size_t)B * prow * sizeof(double)));
+  const size_t sum_doubles = (size_t)max_inst_b * row;
+  if (rho_sum) DTC_TRY(ensure(ctx->rdmb_sum, sum_doubles * sizeof(double)));
+  DTC_TRY(ensure_host(ctx->host_f, (rho_sum ? sum_doubles : 0) + (size_t)B * prow));
+  double* const hs = ctx->host_f.p;
+  double* const hp = hs + (rho_sum ? sum_doubles : 0);
+  std::vector<int64_t> masks(B);
+
+  double2* const F = (double2*)ctx->F.p;
+  double* const pv = (double*)ctx->vals_f.p;
+  double* const dsum = (double*)ctx->rdmb_sum.p;
+  std::vector<Launch> sched = build_sample_schedule(rc, F);
+  // rows the device does not write (t < t_first, and p = 0, formed above)
+  const int t0 = std::max(pr->t_first, pr->t_offset == 0 ? 1 : 0);
+
+  for (int64_t bs = 0; bs < S; bs += B) {
+    const int nb = (int)std::min<int64_t>(B, S - bs);
+    const int64_t i0 = bs / n_traj, n_ib = (bs + nb - 1) / n_traj - i0 + 1;
+    DTC_TRY(batch_masks(ctx, rc, bs, nb, masks));
+    DTC_TRY(basis_source(ctx, sched, F, pl.len, nb, bt.octet));
+    DTC_HIP(hipMemsetAsync(pv, 0, (size_t)B * prow * sizeof(double), ctx->stream));
+    const AfterLaunch measure = [&](const Launch& l) -> int {
+      for (int32_t w = 0; w < n_blk; ++w) {
+        const rb::Geom& g = geo[w];
+        const size_t slot = (size_t)l.t_state * n_blk + w;
+        dtc::RdmBlockArgs A{};
+        A.state = F;
+        A.partial = (double*)ctx->rdmb_part.p;
+        A.work = (double*)ctx->rdmb_work.p;
+        A.work_stride = (int64_t)mat;
+        A.purity = pv + slot;
+        A.purity_stride = (int64_t)prow;
+        A.L_eff = pl.L_eff;
+        A.octet_bits = rc.octet_bits;
+        A.batch = nb;
+        A.g = g;
+        const bool direct = g.n_split == 1 && g.n_pad == 1;
+        if (direct) A.partial = A.work;  // (unused)
+        // the Gram launch reads a panel pair per tile; booked with the batch's
+        // 16 B per amplitude plus the matrices written
+        DTC_TIMED(ctx, DTC_KERNEL_REDUCE,
+                  16.0 * (double)pl.len * nb + 8.0 * nb * (double)mat,
+                  dtc::launch_rdm_block_gram(A, ctx->stream));
+        if (purity) {
+          DTC_TIMED(ctx, DTC_KERNEL_REDUCE, 8.0 * nb * (double)(mat + 1),
+                    dtc::launch_rdm_block_purity(A, ctx->stream));
+        }
+        if (rho_sum) {
+          DTC_TIMED(ctx, DTC_KERNEL_REDUCE, 8.0 * (double)(nb + n_ib) * (double)mat,
+                    dtc::launch_traj_sum(A.work, nb, (int)mat, bs, n_traj,
+                                         dsum + slot * (size_t)max_inst_b * mat, ctx->stream));
+        }
+      }
+      return DTC_OK;
+    };
+    DTC_TRY(run_launches(ctx, rc, bs, nb, sched, measure));
+    if (rho_sum)
+      DTC_HIP(hipMemcpyAsync(hs, dsum, sum_doubles * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    if (purity)
+      DTC_HIP(hipMemcpyAsync(hp, pv, (size_t)nb * prow * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+    DTC_HIP(hipStreamSynchronize(ctx->stream));
+    DTC_TRY(settle_pending(ctx));
+    if (rho_sum)
+      for (int t = t0; t < T; ++t)
+        for (int32_t w = 0; w < n_blk; ++w) {
+          const size_t slot = (size_t)t * n_blk + w;
+          for (int64_t r = 0; r < n_ib; ++r) {
+            // (an instance's trajectories may span batches)
+            const double* v = hs + (slot * (size_t)max_inst_b + (size_t)r) * mat;
+            double* o = rho_sum + (size_t)(i0 + r) * row + slot * mat;
+            for (size_t i = 0; i < mat; ++i) o[i] += v[i];
+          }
+        }
+    if (purity)
+      for (int b = 0; b < nb; ++b)
+        for (size_t i = (size_t)t0 * n_blk; i < prow; ++i)
+          purity[(size_t)(bs + b) * prow + i] = hp[(size_t)b * prow + i];
+  }
+  return DTC_OK;
+}
+
+int dtc_rdm_block_state(const double* state, int32_t L, int32_t start, int32_t k, double* rho,
+                        double* purity) {
+  namespace rb = dtc::rdmb;
+  if (!state || !purity) return fail(DTC_EINVAL, "null argument");
+  if (const char* err = rb::check_block(start, k, L)) return fail(DTC_EINVAL, err);
+  const size_t d = (size_t)1 << k;
+  // the block's own bits are the row: no pad on the host (ke = k, ae = start)
+  std::vector<double> re(d * d, 0.0), im(d * d, 0.0), vr(d), vi(d);
+  const uint64_t n_cols = (uint64_t)1 << (L - k);
+  // the lower triangle by plain sums over the column index in ascending order
+  for (uint64_t c = 0; c < n_cols; ++c) {
+    for (size_t a = 0; a < d; ++a) {
+      const uint64_t x = rb::amp_index(start, k, a, c);
+      vr[a] = state[2 * x];
+      vi[a] = state[2 * x + 1];
+    }
+    for (size_t a = 0; a < d; ++a) {
+      const double ar = vr[a], ai = vi[a];
+      double* rr = &re[a * d];
+      double* ri = &im[a * d];
+      for (size_t a2 = 0; a2 <= a; ++a2) {
+        rr[a2] += ar * vr[a2] + ai * vi[a2];
+        ri[a2] += ai * vr[a2] - ar * vi[a2];
+      }
+    }
+  }
+  double pur = 0.0;
+  for (size_t a = 0; a < d; ++a)
+    for (size_t a2 = 0; a2 <= a; ++a2) {
+      const double gr = re[a * d + a2], gi = a == a2 ? 0.0 : im[a * d + a2];
+      pur += (a == a2 ? 1.0 : 2.0) * (gr * gr + gi * gi);
+      if (!rho) continue;
+      rho[2 * (a * d + a2)] = gr;
+      rho[2 * (a * d + a2) + 1] = gi;
+      if (a == a2) continue;
+      rho[2 * (a2 * d + a)] = gr;
+      rho[2 * (a2 * d + a) + 1] = -gi;
+    }
+  *purity = pur;
   return DTC_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include "dtc_pass_frame.h"
 #include "dtc_rdm.h"
+#include "dtc_rdm_block.h"
 
 namespace dtc {
 
@@ -542,5 +543,29 @@ struct RdmArgs {
 };
 hipError_t launch_rdm_gram(const RdmArgs& a, hipStream_t stream);
 hipError_t launch_rdm_reduce(const RdmArgs& a, hipStream_t stream);
+
+// Reduced density matrices of blocks of 5..10 contiguous sites
+// (dtc_rdm_block.hip, dtc_rdm_block.h; include/dtc.h dtc_rdm_block_sums): the
+// Hermitian d x d matrix of one block of every state of a batch into
+// work[b * work_stride + (a d + a') 2 + re/im].
+//  * gram: one workgroup per lower-triangle 64 x 64 tile, state and column
+//    split (FP64 MFMA); with one split and no pad bit it writes the work matrix
+//    itself, otherwise partial[b][split][de][de][2] and a second launch (finish:
+//    splits in ascending order, block trace over the pad, the conjugate mirror);
+//  * purity: sum |G|^2 of each work matrix in a fixed order into
+//    purity[b * purity_stride].
+struct RdmBlockArgs {
+  const double2* state;    // the batch, in the layout of octet_bits
+  double* partial;         // [batch][n_split][de][de][2] (unused: one split, no pad)
+  double* work;            // [batch] matrices [d][d][2], work_stride doubles apart
+  int64_t work_stride;
+  double* purity;          // purity launch only
+  int64_t purity_stride;
+  int L_eff, octet_bits;
+  int batch;
+  rdmb::Geom g;            // rdmb::geometry(start, k, L_eff)
+};
+hipError_t launch_rdm_block_gram(const RdmBlockArgs& a, hipStream_t stream);
+hipError_t launch_rdm_block_purity(const RdmBlockArgs& a, hipStream_t stream);
 
 }  // namespace dtc

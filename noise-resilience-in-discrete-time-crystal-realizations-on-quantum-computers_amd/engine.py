@@ -266,6 +266,38 @@ def rdm_state(psi, L: int, sites) -> np.ndarray:
     return rho
 
 
+def block_array(blocks) -> np.ndarray:
+    """``blocks`` (one ``(start, k)`` pair, or a list of them of one size k) as
+    an int32 [n_blk][2] array.  Validity is the library's to check."""
+    b = np.asarray(blocks, dtype=np.int64)
+    if b.ndim == 1:
+        b = b[None, :]
+    if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] != 2:
+        raise ValueError("blocks must be (start, k) pairs of one size k")
+    if np.any(b[:, 1] != b[0, 1]):
+        raise ValueError("all blocks of a call share one size k")
+    return np.ascontiguousarray(b.astype(np.int32))
+
+
+def rdm_block_state(psi, L: int, start: int, k: int):
+    """Host only (dtc_rdm_block_state), the block contract's reference: the
+    complex128 [d][d] matrix of the block of sites ``start .. start + k - 1``
+    (5 <= k <= 10, 2 k <= L) of the state ``psi`` (2^L amplitudes, site i =
+    bit i) and its purity ``sum |rho|^2``; bit m of a row index is the bit of
+    site ``start + m``.  Returns ``(rho, purity)``."""
+    lib = _capi.load_library()
+    buf = np.ascontiguousarray(np.asarray(psi, dtype=np.complex128).reshape(-1))
+    if not 1 <= L <= 32 or buf.size != 1 << L:
+        raise ValueError("psi must hold 2^L amplitudes, 1 <= L <= 32")
+    d = 1 << k if 5 <= k <= 10 else 1  # (a bad k is the library's to refuse)
+    rho = np.zeros((d, d), dtype=np.complex128)
+    pur = np.zeros(1)
+    _capi.check(lib.dtc_rdm_block_state(
+        _capi.as_dptr(buf.view(np.float64)), ctypes.c_int32(L), ctypes.c_int32(start),
+        ctypes.c_int32(k), _capi.as_dptr(rho.view(np.float64)), _capi.as_dptr(pur)))
+    return rho, float(pur[0])
+
+
 def bond_struct(p_bond: np.ndarray) -> "_capi.DtcBondNoise":
     b = _capi.DtcBondNoise()
     b.p_bond = _capi.as_dptr(p_bond)
@@ -717,6 +749,35 @@ class DtcEngine:
         for the noise-averaged state."""
         return self._rdm("dtc_rdm_sums", "rdm_sums", spec, (spec.n_inst,), n_traj, windows,
                          seed, traj_offset, batch, t_first)
+
+    def rdm_block_sums(self, spec: SweepSpec, n_traj: int, blocks, seed: int = 0x5EED0001,
+                       traj_offset: int = 0, batch: int = 0, t_first: int = 0) -> dict:
+        """Reduced density matrices of blocks of contiguous sites of the forward
+        sweep (dtc_rdm_block_sums).  ``blocks`` is one ``(start, k)`` pair or a
+        list of them of one size 5 <= k <= 10, 2 k <= L.  Returns ``rho_sum``,
+        complex128 [n_inst][T][n_blk][d][d], the sum over each instance's
+        trajectories of the per-state rho (divide by ``n_traj`` for the
+        noise-averaged state); ``purity`` [n_inst][n_traj][T][n_blk], ``Tr rho^2``
+        of every trajectory's own state (``-ln`` of it: the trajectory-resolved
+        second Renyi entanglement entropy); ``blocks`` int32 [n_blk][2].  Rows
+        before ``t_first`` stay 0.  Depolarizing or noiseless kicks only."""
+        refuse_rdm(spec, "rdm_block_sums")
+        blk = block_array(blocks)
+        n_blk, k = blk.shape[0], int(blk[0, 1])
+        if not 5 <= k <= 10:
+            raise ValueError(f"block size must be in [5, 10], got {k} (k <= 4: rdm)")
+        d = 1 << k
+        n_traj = int(n_traj)
+        starts = np.ascontiguousarray(blk[:, 0])
+        rho = np.zeros((spec.n_inst, spec.T, n_blk, d, d), dtype=np.complex128)
+        pur = np.zeros((spec.n_inst, n_traj, spec.T, n_blk))
+        pr = self._problem(spec, True, False, batch, t_first)
+        _capi.check(self._lib.dtc_rdm_block_sums(
+            self._ctx, ctypes.byref(pr), ctypes.byref(self._noise(spec)), ctypes.c_uint64(seed),
+            ctypes.c_int64(traj_offset), ctypes.c_int32(n_traj),
+            starts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.c_int32(n_blk),
+            ctypes.c_int32(k), _capi.as_dptr(rho.view(np.float64)), _capi.as_dptr(pur)))
+        return {"rho_sum": rho, "purity": pur, "blocks": blk}
 
     # -- sharded state (dtc_shard_*; driver: sharded.py) ----------------
     def shard_set_basis(self, spec: SweepSpec, shard, state_ptr: int, seed: int = 0x5EED0001,

@@ -9,6 +9,14 @@ mutual information are *not* linear in rho: take them of the trajectory mean
 (``get_instances_rdm``), never average them per trajectory.  The names here have
 no counterpart in the reference.
 
+Blocks of 5..10 contiguous sites -- the half chain up to L = 20 -- come from
+``DtcEngine.rdm_block_sums`` (dtc_rdm_block_sums): the trajectory mean of rho_A
+as above (``get_instances_block``), and the purity ``Tr rho_A^2`` of every
+trajectory's own pure state, whose ``-ln`` is the trajectory-resolved second
+Renyi *entanglement* entropy: that one is averaged per trajectory
+(``renyi2_traj``), and in a noiseless run equals the Renyi-2 entropy of the mean.
+``entanglement_profile`` takes every cut of the chain.
+
 Index convention (the C ABI's): for a window of sites ``s_0 < ... < s_{k-1}`` bit
 m of a row index is the bit of ``s_m``; an operator on the window is
 ``kron(O_{s_{k-1}}, ..., O_{s_0})``.
@@ -17,7 +25,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import SweepSpec, refuse_rdm, window_array
+from .engine import SweepSpec, block_array, refuse_rdm, window_array
 from .energy import ESTIMATOR_SHOTS, _engine
 
 PAULI = np.array([[[1, 0], [0, 1]], [[0, 1], [1, 0]], [[0, -1j], [1j, 0]], [[1, 0], [0, -1]]],
@@ -123,3 +131,72 @@ def get_instances_rdm(spec: SweepSpec, n_traj: int = ESTIMATOR_SHOTS, windows=((
     rho = _engine(engine).rdm_sums(spec, n_traj, win, seed=seed, traj_offset=traj_offset) / n_traj
     return {"rho": rho, "entropy": von_neumann_entropy(rho), "purity": purity(rho),
             "windows": win}
+
+
+MAX_BLOCK = 10   # dtc_rdm_block_sums' largest block; dtc_rdm's is 4
+
+
+def get_instances_block(spec: SweepSpec, n_traj: int = ESTIMATOR_SHOTS, blocks=((0, 5),),
+                        seed: int = 0x5EED0001, engine=None, traj_offset: int = 0,
+                        batch: int = 0) -> dict:
+    """Blocks of 5..10 contiguous sites, ``blocks`` = ``(start, k)`` pairs of one
+    size (``DtcEngine.rdm_block_sums``): ``rho`` ``[n_inst][T][n_blk][d][d]`` the
+    trajectory mean, ``entropy`` and ``purity`` ``[n_inst][T][n_blk]`` of that
+    mean, ``renyi2_traj`` ``[n_inst][T][n_blk]`` the trajectory mean of
+    ``-ln Tr rho_A^2`` of each trajectory's own state, ``blocks`` int32
+    ``[n_blk][2]``."""
+    refuse_rdm(spec, "get_instances_block")
+    res = _engine(engine).rdm_block_sums(spec, n_traj, block_array(blocks), seed=seed,
+                                         traj_offset=traj_offset, batch=batch)
+    rho = res["rho_sum"] / n_traj
+    return {"rho": rho, "entropy": von_neumann_entropy(rho), "purity": purity(rho),
+            "renyi2_traj": -np.log(res["purity"]).mean(axis=1), "blocks": res["blocks"]}
+
+
+def profile_blocks(L: int) -> list:
+    """The block ``(start, k)`` of every cut l = 1 .. L-1 of the chain (between
+    sites l-1 and l): the smaller side, the left one ``[0, l)`` on a tie.  A pure
+    state's two sides have the same spectrum, so either gives the cut's entropy.
+    Refuses an L with a cut whose smaller side exceeds ``MAX_BLOCK`` sites."""
+    if L < 2:
+        raise ValueError("a cut needs L >= 2")
+    if L // 2 > MAX_BLOCK:
+        raise ValueError(f"L = {L}: the middle cuts' smaller side has {L // 2} sites, "
+                         f"more than the {MAX_BLOCK} a block can have")
+    return [(0, l) if l <= L - l else (l, L - l) for l in range(1, L)]
+
+
+def entanglement_profile(spec: SweepSpec, n_traj: int = ESTIMATOR_SHOTS,
+                         seed: int = 0x5EED0001, engine=None, traj_offset: int = 0) -> dict:
+    """The entanglement across every cut of the chain: ``renyi2_traj``
+    ``[n_inst][T][L-1]``, the trajectory mean of ``-ln Tr rho_A^2`` of each
+    trajectory's own state, A the smaller side of cut l (``profile_blocks``); for
+    a noiseless spec also ``entropy`` ``[n_inst][T][L-1]``, the von Neumann
+    entanglement entropy of the (single) state.  Sides of up to four sites go
+    through ``DtcEngine.rdm`` with the purity of each trajectory's matrix taken
+    here, sides of 5..10 through ``rdm_block_sums``.  ``blocks``: int32
+    ``[L-1][2]``."""
+    refuse_rdm(spec, "entanglement_profile")
+    L, T = spec.L, spec.T
+    blocks = profile_blocks(L)
+    eng = _engine(engine)
+    noiseless = not spec.p > 0
+    r2 = np.zeros((spec.n_inst, T, L - 1))
+    ent = np.zeros((spec.n_inst, T, L - 1)) if noiseless else None
+    for k in sorted({k for _, k in blocks}):
+        cuts = [c for c, (_, kk) in enumerate(blocks) if kk == k]
+        if k <= 4:
+            rho = eng.rdm(spec, n_traj, [list(range(blocks[c][0], blocks[c][0] + k)) for c in cuts],
+                          seed=seed, traj_offset=traj_offset)
+            pur, mean = purity(rho), rho.mean(axis=1)
+        else:
+            res = eng.rdm_block_sums(spec, n_traj, [blocks[c] for c in cuts], seed=seed,
+                                     traj_offset=traj_offset)
+            pur, mean = res["purity"], res["rho_sum"] / n_traj
+        r2[:, :, cuts] = -np.log(pur).mean(axis=1)
+        if noiseless:
+            ent[:, :, cuts] = von_neumann_entropy(mean)
+    out = {"renyi2_traj": r2, "blocks": np.asarray(blocks, dtype=np.int32)}
+    if noiseless:
+        out["entropy"] = ent
+    return out

@@ -17,6 +17,23 @@ Written under ``--out_dir`` into ``entanglement-data_L{L}/``:
     entanglement_rho_....npy
             the instance-averaged mean matrices, complex ``[T][n_win][d][d]``
 
+Blocks of 5..10 contiguous sites (``entanglement.get_instances_block``):
+``--block_size k`` with one ``--block_start a`` per block (default 0) writes,
+instead of the windows' files,
+
+    entanglement_block_data_....csv
+            columns time, then entropy_b{a}-{a+k-1}, purity_b.. (of the
+            trajectory-mean rho_A) and renyi2_traj_b.. (the trajectory mean of
+            -ln Tr rho_A^2 of each trajectory's own state) per block
+    entanglement_block_rho_....npy
+            the instance-averaged mean matrices, complex ``[T][n_blk][d][d]``
+
+and ``--profile 1`` (``entanglement.entanglement_profile``) writes
+
+    entanglement_profile_....csv
+            columns time, then renyi2_traj_cut{l} for every cut l = 1 .. L-1
+            and, without noise, entropy_cut{l}
+
 The sites' initial state is the autocorrelator's (``neel`` = X on sites 1, 3,
 ...).  Depolarizing or noiseless kicks only.
 """
@@ -55,6 +72,12 @@ def build_parser():
                    help="sliding block of adjacent sites (without --window_sites)")
     p.add_argument("--window_start", type=int, default=0)
     p.add_argument("--window_stride", type=int, default=1)
+    p.add_argument("--block_size", type=int, default=None, choices=[5, 6, 7, 8, 9, 10],
+                   help="blocks of this many contiguous sites (instead of windows)")
+    p.add_argument("--block_start", type=int, action="append", default=None,
+                   help="first site of a block (repeatable; default 0)")
+    p.add_argument("--profile", type=int, default=0, choices=[0, 1],
+                   help="1: the Renyi-2 entanglement across every cut of the chain")
     p.add_argument("--trajectories", type=int, default=1024,
                    help="noisy trajectories per instance (1 is used without noise)")
     p.add_argument("--seed", type=int, default=0x5EED0001)
@@ -85,6 +108,28 @@ def windows_from_args(args) -> np.ndarray:
     return np.asarray(wins, dtype=np.int32)
 
 
+def blocks_from_args(args):
+    """The int32 ``[n_blk][2]`` ``(start, k)`` blocks the flags name, or None
+    without ``--block_size``."""
+    k = args.block_size
+    if k is None:
+        if args.block_start is not None:
+            raise ValueError("--block_start needs --block_size")
+        return None
+    starts = args.block_start if args.block_start is not None else [0]
+    if 2 * k > args.L:
+        raise ValueError(f"--block_size {k}: a block has at most L / 2 = {args.L // 2} sites")
+    for a in starts:
+        if a < 0 or a + k > args.L:
+            raise ValueError(f"block of {k} sites from site {a} does not fit L = {args.L}")
+    return np.asarray([[a, k] for a in starts], dtype=np.int32)
+
+
+def block_label(block) -> str:
+    a, k = int(block[0]), int(block[1])
+    return f"b{a}-{a + k - 1}"
+
+
 def window_label(sites) -> str:
     return "s" + "-".join(str(int(s)) for s in sites)
 
@@ -104,22 +149,53 @@ def main(argv=None):
 
     args = build_parser().parse_args(argv)
     L, T = args.L, args.tf
-    wins = windows_from_args(args)
+    blocks = blocks_from_args(args)
+    wins = windows_from_args(args) if blocks is None and not args.profile else None
     hs, phis = load_disorder(L, args.inst, args.disorder_folder)
     spec = SweepSpec(L=L, T=T, hs=hs, phis=phis, g=args.g, polarization=args.polarization,
                      circular_frequency=args.circular_frequency,
                      initial_state=args.initial_state, noise_prob=args.noise_prob,
                      use_noise=args.use_noise)
     n_traj = args.trajectories if spec.p > 0 else 1
+    name_args = (args.initial_state, args.g, L, args.inst, T, args.randomphi, args.phi_delta,
+                 args.phi_amplitude, args.noise_prob, args.use_noise)
+    folder = os.path.join(args.out_dir, entanglement_folder(L))
+    if args.profile:
+        os.makedirs(folder, exist_ok=True)
+        prof = en.entanglement_profile(spec, n_traj, seed=args.seed)
+        cols = {"time": np.arange(0, T)}
+        for key in ("renyi2_traj", "entropy"):
+            if key in prof:
+                for c in range(L - 1):
+                    cols[f"{key}_cut{c + 1}"] = prof[key][:, :, c].mean(axis=0)
+        path = os.path.join(folder, entanglement_file_name("entanglement_profile", "csv",
+                                                           *name_args))
+        pd.DataFrame(cols).to_csv(path, index=False)
+        print(f"Entanglement profile saved to {path}")
+        if blocks is None:
+            return 0
+    if blocks is not None:
+        os.makedirs(folder, exist_ok=True)
+        res = en.get_instances_block(spec, n_traj, blocks, seed=args.seed)
+        cols = {"time": np.arange(0, T)}
+        for key in ("entropy", "purity", "renyi2_traj"):
+            for w, blk in enumerate(blocks):
+                cols[f"{key}_{block_label(blk)}"] = res[key][:, :, w].mean(axis=0)
+        path = os.path.join(folder, entanglement_file_name("entanglement_block_data", "csv",
+                                                           *name_args))
+        pd.DataFrame(cols).to_csv(path, index=False)
+        print(f"Block entanglement data saved to {path}")
+        mpath = os.path.join(folder, entanglement_file_name("entanglement_block_rho", "npy",
+                                                            *name_args))
+        np.save(mpath, res["rho"].mean(axis=0))
+        print(f"Mean block density matrices saved to {mpath}")
+        return 0
     res = en.get_instances_rdm(spec, n_traj, wins, seed=args.seed)
     cols = {"time": np.arange(0, T)}
     for w, sites in enumerate(wins):
         cols["entropy_" + window_label(sites)] = res["entropy"][:, :, w].mean(axis=0)
     for w, sites in enumerate(wins):
         cols["purity_" + window_label(sites)] = res["purity"][:, :, w].mean(axis=0)
-    name_args = (args.initial_state, args.g, L, args.inst, T, args.randomphi, args.phi_delta,
-                 args.phi_amplitude, args.noise_prob, args.use_noise)
-    folder = os.path.join(args.out_dir, entanglement_folder(L))
     os.makedirs(folder, exist_ok=True)
     path = os.path.join(folder, entanglement_file_name("entanglement_data", "csv", *name_args))
     pd.DataFrame(cols).to_csv(path, index=False)
